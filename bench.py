@@ -10,7 +10,11 @@ RCCL (+ the xGMI engine).  Each timed step = data gather + forward + loss +
 backward (+ SyncBN / DDP all-reduces) + unscale/inf-check + SGD + scale
 update, replayed from captured hipGraphs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+        A plain run measures the headline only: set-up, exactly W untimed and K timed
+        steps, then the JSON line (``value``, ``ms_per_step``).  ``--dump-outputs DIR``
+        writes what the last timed step computed as DIR/<name>.npy (_dump_outputs).
+        ``--full`` adds everything else listed under "What one rank measures".
         N > 1 without WORLD_SIZE in the environment: this process supervises N
         fresh rank processes (one per GPU, like the reference's mp.spawn,
         /root/reference/ddp_main.py:173-178) and never touches the GPU itself.
@@ -28,12 +32,13 @@ Fail-safe multi-GPU runs (N > 1):
     by the supervisors as fresh processes with ``--comm rccl`` (no xGMI engine, no
     in-kernel exchanges; ``--share-gpu``: ``--comm host``) and the line says
     ``"fallback"`` plus the original ``comm_error``;
-  * a successful ``--comm auto`` run with the xGMI engine on is followed by an A/B
-    attempt on ``--comm rccl`` (headline only) -> ``ab`` keys.
+  * ``--full``: a successful ``--comm auto`` run with the xGMI engine on is followed by
+    an A/B attempt on ``--comm rccl`` (headline only) -> ``ab`` keys.
   Exit status: 0 = a measured line (possibly after a fallback); 3 = every attempt
   failed (the line then has ``value`` null and ``comm_error``); 2 = bad arguments.
 
-What one rank measures (rank 0's record becomes the JSON line):
+What one rank measures (rank 0's record becomes the JSON line; a plain run: the
+first half of item 2 only, ``--full``: all of it):
   1. the reference's whole program on this node: 3 epochs over the 60k-sample
      train set (DistributedSampler shards, graph-replayed full batches + the
      eager tail batch) and the sharded test pass -> ``wall_3epoch_s``,
@@ -68,6 +73,7 @@ METRIC = "images/sec (whole node) + 3-epoch wall-clock, MNIST ConvNet at 1/2/4/8
 PUBLISHED_IMG_S = {1: 7923.0, 2: 5840.0}
 PUBLISHED_WALL_S = {1: 22.72, 2: 30.82}
 _DT = {"bf16": "bfloat16", "fp16": "float16", "fp32": None}
+_DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much in all (plus the small arrays)
 
 
 def parse(argv=None):
@@ -108,7 +114,18 @@ def parse(argv=None):
     ap.add_argument("--train-samples", type=int, default=60000, help="synthetic train-set size (tests only)")
     ap.add_argument("--test-samples", type=int, default=10000, help="synthetic test-set size (tests only)")
     ap.add_argument("--out", default=None, help="also append the JSON line to this file")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the 3-epoch program, the steady state, "
+                         "the other precisions, the same-node torch baseline and (N > 1) the --comm rccl A/B; "
+                         "without it --epochs / --extra-dtypes / --baseline-steps have nothing to act on")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (loss, logits, updated "
+                         "parameters and buffers, loss scale) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.epochs, args.extra_dtypes = 0, ""
+        args.no_steady = args.no_baseline = args.no_ab = True
+    return args
 
 
 # ----------------------------------------------------------------------------- entry
@@ -146,17 +163,18 @@ def main(argv=None) -> int:
 
 
 # ----------------------------------------------------------------------------- supervisor (N > 1)
-def _child_argv(argv: list[str], extra: list[str]) -> list[str]:
-    """argv without --comm / --out (the supervisor owns them) plus ``extra``."""
+def _child_argv(argv: list[str], extra: list[str], drop: tuple = ()) -> list[str]:
+    """argv without --comm / --out (the supervisor owns them) and the ``drop`` options, plus ``extra``."""
     out, skip = [], False
+    owned = ("--comm", "--out", *drop)
     for a in argv:
         if skip:
             skip = False
             continue
-        if a in ("--comm", "--out"):
+        if a in owned:
             skip = True
             continue
-        if a.startswith("--comm=") or a.startswith("--out="):
+        if a.startswith(tuple(o + "=" for o in owned)):
             continue
         out.append(a)
     return [sys.executable, os.path.abspath(__file__), *out, *extra]
@@ -201,9 +219,10 @@ def supervise(args, argv: list[str]) -> int:
     fb_mode = "host" if args.share_gpu else "rccl"
     attempts = []
 
-    def attempt(m: str, extra: list[str], env_over: dict, tag: str, timeout=None):
+    def attempt(m: str, extra: list[str], env_over: dict, tag: str, timeout=None, drop: tuple = ()):
         ta = time.time()
-        res = sup.run(_child_argv(argv, ["--comm", m, *extra]), {**env, **env_over}, tag=tag, timeout_s=timeout)
+        res = sup.run(_child_argv(argv, ["--comm", m, *extra], drop), {**env, **env_over}, tag=tag,
+                      timeout_s=timeout)
         err = summarize(res)
         attempts.append({"comm": m, "tag": tag, "ok": not err, "error": err, "seconds": round(time.time() - ta, 2),
                          "xgmi_status": [(r.status or {}).get("xgmi_status") for r in res]})
@@ -221,7 +240,7 @@ def supervise(args, argv: list[str]) -> int:
     if (rec is not None and gpu and not args.share_gpu and not args.no_ab and mode == "auto" and fallback is None
             and args.model == "convnet" and str(rec.get("config", {}).get("comm", "")).find("xgmi on") >= 0):
         _, ab_err, ab_rec = attempt("rccl", ["--epochs", "0", "--no-baseline", "--extra-dtypes", "", "--no-steady"],
-                                    {}, "ab-rccl", timeout=180)
+                                    {}, "ab-rccl", timeout=180, drop=("--dump-outputs",))
         ab = {"auto_ms_per_step": rec.get("ms_per_step"), "auto_img_s": rec.get("value")}
         if ab_rec is not None:
             ab.update(rccl_ms_per_step=ab_rec.get("ms_per_step"), rccl_img_s=ab_rec.get("value"),
@@ -371,8 +390,13 @@ class _Chunks:
     """Exactly ``n`` training steps as replays of a K-step graph plus one graph of the remainder,
     keeping the loader's device step counter inside the epoch's full batches."""
 
-    def __init__(self, step, spg: int, loader, nfull: int, graphs: bool, health: _Health | None = None):
+    def __init__(self, step, spg: int, loader, nfull: int, graphs: bool, health: _Health | None = None,
+                 last: dict | None = None):
         from ddp_practice_amd.runtime import CapturedStep
+
+        # ``last``: the dict ``step`` leaves its results in.  A graph's replay writes the tensors
+        # that were in it when that graph was captured, so every runner keeps its own (``kept``).
+        self.last, self.kept, self.last_k = last, {}, None
 
         self.step, self.spg, self.loader, self.nfull = step, max(1, spg), loader, nfull
         self.graphs = graphs
@@ -389,6 +413,8 @@ class _Chunks:
             r = self._mk(k)
             if self.graphs and not r.capture():
                 self.capture_error = r.capture_error
+            if self.last is not None:
+                self.kept[k] = dict(self.last)
             self.loader.set_step(0)
             self.pos = 0
             self.runners[k] = r
@@ -432,6 +458,12 @@ class _Chunks:
             self.pos = 0
         self.runners[k].run()
         self.pos += k
+        self.last_k = k
+
+    def outputs(self) -> dict:
+        """What the last step of the last ``run`` left in ``last`` (synchronize first)."""
+        r = self.runners.get(self.last_k)
+        return self.kept[self.last_k] if r is not None and r.graph is not None else dict(self.last or {})
 
     def run(self, n: int) -> None:
         tick = self.health.tick if self.health is not None else None
@@ -510,10 +542,11 @@ def run_rank(args) -> int:
 
     # 2. the headline: exactly K timed steps after exactly W warm-up steps (+ steady state)
     amp = _amp(args.amp_dtype)
+    dump = args.dump_outputs if rank == 0 else None
     if args.impl == "native":
-        h = _headline(ctx, amp, steady=not args.no_steady)
+        h = _headline(ctx, amp, steady=not args.no_steady, dump=dump)
     else:
-        h = _torch_headline(ctx, amp)
+        h = _torch_headline(ctx, amp, dump=dump)
     health.check("headline")
     ms, img_s = h["ms"], h["img_s"]
     if "steady_img_s" in h:
@@ -627,6 +660,35 @@ def _build(ctx, amp, seed: int):
     return model, SGD(model.parameters(), lr=1e-4), GradScaler(enabled=amp is not None)
 
 
+def _dump_outputs(dirname: str, model, scaler, last: dict) -> None:
+    """--dump-outputs: what a caller of the timed step holds after its last step, one
+    ``<name>.npy`` each: ``loss`` and ``logits`` of that step's batch, every updated parameter
+    (``param.<key>``) and buffer (``buffer.<key>``, the BatchNorm running statistics) under
+    its state_dict key, and the loss scale.  float32; integer buffers as float64.  The data,
+    the initial weights and the sample order are seeded, so equal arguments give equal inputs.
+    Above _DUMP_BYTES in all (ResNet-50) every large array is cut to the same fraction of its
+    elements, flattened, at sorted positions drawn once from a fixed seed."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    net = getattr(model, "module", model)
+    arrays = dict(last)
+    arrays.update({f"param.{k}": p for k, p in net.named_parameters()})
+    arrays.update({f"buffer.{k}": b for k, b in net.named_buffers()})
+    if scaler is not None:
+        arrays["loss_scale"] = torch.tensor([scaler.get_scale()], dtype=torch.float32)
+    total = sum(4 * t.numel() for t in arrays.values())
+    frac = min(1.0, _DUMP_BYTES / max(total, 1))
+    rng = np.random.default_rng(0)
+    for name, t in arrays.items():
+        t = t.detach()
+        a = (t.float() if t.is_floating_point() else t.double()).cpu().numpy()
+        if frac < 1.0 and a.size > 4096:
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, int(a.size * frac), replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def _three_epochs(ctx) -> dict:
     import torch
 
@@ -690,9 +752,10 @@ def _three_epochs(ctx) -> dict:
     return out
 
 
-def _headline(ctx, amp, steady: bool) -> dict:
+def _headline(ctx, amp, steady: bool, dump: str | None = None) -> dict:
     """Exactly --warmup untimed + --steps timed steps of the native step (graph replays),
-    then (``steady``) at least one full epoch of replays timed the same way."""
+    then (``steady``) at least one full epoch of replays timed the same way.  ``dump``: the
+    directory that receives the last timed step's results (_dump_outputs)."""
     import torch
 
     from ddp_practice_amd import distributed as ddist
@@ -719,10 +782,14 @@ def _headline(ctx, amp, steady: bool) -> dict:
     nfull = len(sampler) // B
     defer = accepts_deferred(model, images)  # the gather runs inside conv1
 
+    last = {} if dump else None  # --dump-outputs: the step's own results (_Chunks.outputs)
+
     def step():
         loader.fill_(images, labels, defer=defer)
         out = model(images)
         loss = crit(out, labels)
+        if last is not None:
+            last["logits"], last["loss"] = out.detach(), loss.detach()
         optimizer.zero_grad(set_to_none=True)
         if amp is not None:
             scaler.scale(loss).backward()
@@ -733,7 +800,7 @@ def _headline(ctx, amp, steady: bool) -> dict:
             optimizer.step()
 
     spg = 1 if args.no_graph else args.steps_per_graph
-    chunks = _Chunks(step, spg, loader, nfull, graphs=not args.no_graph, health=health)
+    chunks = _Chunks(step, spg, loader, nfull, graphs=not args.no_graph, health=health, last=last)
     n_steady = max(nfull, args.steps) if steady else 0
     for n in (args.warmup, args.steps, n_steady):
         if n:
@@ -766,6 +833,8 @@ def _headline(ctx, amp, steady: bool) -> dict:
 
     chunks.run(args.warmup)
     dt = timed(args.steps)
+    if dump:
+        _dump_outputs(dump, model, scaler if amp is not None else None, chunks.outputs())
     out = {"dt": dt, "ms": dt / args.steps * 1e3, "img_s": B * world * args.steps / dt,
            "captured": chunks.graphs and chunks.capture_error is None, "spg": spg,
            "impl": "native (fused HIP kernels, C++ reducer/communicator)" if ctx["gpu"] else
@@ -780,7 +849,7 @@ def _headline(ctx, amp, steady: bool) -> dict:
     return out
 
 
-def _torch_headline(ctx, amp) -> dict:
+def _torch_headline(ctx, amp, dump: str | None = None) -> dict:
     from ddp_practice_amd import distributed as ddist
     from ddp_practice_amd.data import DistributedSampler
     from ddp_practice_amd.utils.reference_step import TorchReferenceStep
@@ -791,6 +860,8 @@ def _torch_headline(ctx, amp) -> dict:
                              DistributedSampler(train_ds, num_replicas=world, rank=rank).indices().to(dev),
                              args.batch_size, local_rank=ctx["local_rank"], seed=1)
     dt = ddist.max_over_ranks(ref.time_steps(args.steps, args.warmup, ddist.barrier))
+    if dump:  # torch's step keeps no loss or logits: the updated parameters, buffers and loss scale
+        _dump_outputs(dump, ref.model, ref.scaler if amp is not None else None, {})
     return {"dt": dt, "ms": dt / args.steps * 1e3, "img_s": args.batch_size * world * args.steps / dt,
             "captured": False, "spg": 1,
             "impl": "torch (nn modules, torch.autocast, torch GradScaler/SGD/SyncBatchNorm/DDP)",
@@ -906,6 +977,8 @@ def bench_resnet(args) -> int:
     labels = torch.randint(0, 1000, (bs,), generator=g).to(dev)
     if args.resnet_impl != "native":
         images = images.contiguous(memory_format=torch.channels_last)
+    # --dump-outputs: the step's own results (torchref's step keeps none: parameters and buffers only)
+    last = {} if args.dump_outputs and rank == 0 and not torchref else None
 
     def step():
         if args.resnet_impl == "torch" and amp is not None:
@@ -914,6 +987,8 @@ def bench_resnet(args) -> int:
         else:
             out = model(images)
         loss = cross_entropy(out, labels)
+        if last is not None:
+            last["logits"], last["loss"] = out.detach(), loss.detach()
         optimizer.zero_grad(set_to_none=True)
         scaler.scale(loss).backward()
         scaler.step(optimizer)
@@ -955,6 +1030,9 @@ def bench_resnet(args) -> int:
     ddist.barrier()
     dt = ddist.max_over_ranks(time.perf_counter() - t0)
     health.check("headline")
+    if args.dump_outputs and rank == 0:
+        # one runner, whose graph (or eager step) wrote the tensors that ``last`` holds
+        _dump_outputs(args.dump_outputs, model, None if torchref or amp is None else scaler, last or {})
     ms = dt / args.steps * 1e3
     img_s = bs * world * args.steps / dt
     seen = _ranks_seen(c if dist_path else None)

@@ -14,7 +14,7 @@ timeout -k 10 700 python -u -m pytest tests/test_convnet_fused_gpu.py $TESTS -x 
   --timeout-method thread > $OUT/tests.log 2>&1
 rc=$?; echo "tests rc=$rc"; tail -4 $OUT/tests.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 300 python bench.py --out $OUT/bench.jsonl > $OUT/bench.log 2>&1
+timeout -k 10 300 python bench.py --full --out $OUT/bench.jsonl > $OUT/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; grep -o '"value": [0-9.]*\|"ms_per_step": [0-9.]*\|"vs_baseline": [0-9.]*\|"wall_3epoch_s": [0-9.]*\|"accuracy": [0-9.]*' $OUT/bench.jsonl
 [ $rc -ne 0 ] && exit $rc
 cd /tmp && export TMPDIR=/tmp

@@ -19,7 +19,7 @@ run() {  # name, extra env..., -- bench args
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
   env "${envs[@]}" timeout -k 10 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W \
-    --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) bench.py --gpus $W --share-gpu --no-fallback \
+    --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) bench.py --gpus $W --share-gpu --no-fallback --full \
     "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -40 $OUT/$name.err; return 1; }
   python - "$OUT/$name.json" "$W" <<'EOF'
 import json, sys

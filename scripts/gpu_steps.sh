@@ -15,7 +15,7 @@
 #   steady       ConvNet steady-state kernel table (rocprofv3 kernel trace), plain and forced
 #                (STEADY_MODES="plain forced fp32" adds the fp32 step)
 #   rn_steady    ResNet-50 steady-state kernel table
-#   bench        the driver's bench command and the default 2000-step run
+#   bench        the driver's bench command and the default 2000-step run, both with --full
 #   rn_bench     ResNet-50 bench (bs 128, bf16)
 #   rehearse8    bench.py with 8 ranks sharing the GPU under torchrun (scripts/gpu_rehearse.sh)
 #   cli8         the 8-rank shared-GPU CLI tests (tests/test_cli_gpu.py -k eight; DPA_GPU_W8=1)
@@ -229,8 +229,8 @@ step() {
       python3 scripts/trace_steady.py "$(find "$OUT/prof_rn" -name '*kernel_trace.csv' -print -quit)" amp_sgd 5 \
         > "$OUT/rn_steady.txt" && rm -rf "$OUT/prof_rn" ;;
     bench)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" &&
-      timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" &&
+      timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
     rn_bench)
       timeout -k 10 400 python bench.py --model resnet50 --steps 20 --warmup 5 > "$OUT/rn_bench.json" 2> "$OUT/rn_bench.err" ;;
     rehearse8)

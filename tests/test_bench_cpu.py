@@ -26,7 +26,7 @@ def _json_lines(out):
 
 
 def test_bench_self_launches_two_ranks():
-    r = _bench(["--gpus", "2", "--steps", "7", "--warmup", "3", "--epochs", "1", "--train-samples", "640",
+    r = _bench(["--gpus", "2", "--steps", "7", "--warmup", "3", "--full", "--epochs", "1", "--train-samples", "640",
                 "--test-samples", "128"])
     assert r.returncode == 0, r.stdout + r.stderr
     recs = _json_lines(r.stdout)
@@ -48,7 +48,8 @@ def test_bench_rejects_bad_gpu_count():
     assert r.returncode == 2 and "--gpus must be >= 1" in r.stderr
 
 
-_SMALL = ["--gpus", "2", "--steps", "7", "--warmup", "3", "--epochs", "1", "--train-samples", "640",
+# --full: the injected faults (DPA_FAULT) fire inside the epoch program
+_SMALL = ["--gpus", "2", "--steps", "7", "--warmup", "3", "--full", "--epochs", "1", "--train-samples", "640",
           "--test-samples", "128"]
 
 
@@ -107,7 +108,7 @@ def test_bench_under_torchrun_eight_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env["CUDA_VISIBLE_DEVICES"] = ""
-    args = ["--gpus", "8", "--steps", "3", "--warmup", "2", "--epochs", "1", "--train-samples", str(8 * 44),
+    args = ["--gpus", "8", "--steps", "3", "--warmup", "2", "--full", "--epochs", "1", "--train-samples", str(8 * 44),
             "--test-samples", str(8 * 34)]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                         "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
@@ -142,6 +143,69 @@ def test_bench_under_torchrun_rank_failure_falls_back():
     rec = recs[0]
     assert rec["fallback"] == "rccl" and rec["value"] > 0
     assert "rank 0: exit 7" in rec["comm_error"]
+
+
+_PLAIN = ["--gpus", "1", "--steps", "4", "--warmup", "2", "--train-samples", "640", "--test-samples", "128"]
+# what only --full measures
+_FULL_KEYS = ("wall_3epoch_s", "epochs", "accuracy", "steady_img_s", "value_fp16", "value_fp32",
+              "baseline_ms_per_step", "ab")
+
+
+def test_bench_plain_run_measures_the_headline_only(tmp_path):
+    """Without --full: the timed steps and the line, none of the other measurements (even when
+    their own options are given); --dump-outputs writes the last step's arrays, float32 or
+    float64, and a second run with the same arguments starts from the same inputs."""
+    import numpy as np
+
+    dumps = []
+    for d in ("a", "b"):
+        r = _bench([*_PLAIN, "--epochs", "1", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stdout + r.stderr
+        recs = _json_lines(r.stdout)
+        assert len(recs) == 1, r.stdout
+        rec = recs[0]
+        assert rec["steps"] == 4 and rec["warmup"] == 2 and rec["n_gpus"] == 1
+        assert rec["value"] > 0 and rec["unit"] == "images/s" and rec["higher_is_better"] is True
+        assert rec["ms_per_step"] == pytest.approx(32 / rec["value"] * 1e3, rel=1e-3)
+        assert rec["ms_per_step"] == pytest.approx(rec["per_rank_max_s"] / 4 * 1e3, rel=1e-3)
+        assert not [k for k in _FULL_KEYS if k in rec]
+        assert sorted(rec["phases_s"]) == ["end", "headline", "setup"]
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"loss", "logits", "param.fc.weight", "buffer.layer1.1.running_mean"} <= set(a)
+    assert a["logits"].shape == (32, 10) and a["loss"].size == 1 and a["param.fc.weight"].shape == (10, 1568)
+    assert sum(v.size for k, v in a.items() if k.startswith("param.")) == 29034
+    assert a["buffer.layer1.1.num_batches_tracked"].item() == 6  # warm-up + timed steps, nothing else
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.isfinite(a[k]).all(), k
+        # same seeds, same arguments: the CPU path is deterministic up to thread-order rounding
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6, err_msg=k)
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """Above the byte budget every large array is cut to the same seeded positions."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "_DUMP_BYTES", 4 * 20000)
+    net = torch.nn.Linear(100, 300)  # 30,000 + 300 parameters
+    last = {"logits": torch.arange(12000, dtype=torch.float32).reshape(40, 300)}
+    for d in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / d), net, None, last)
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sum(v.nbytes for v in a.values()) <= 4 * 20000 + 4 * 300
+    assert a["param.bias.npy"].shape == (300,)  # small arrays stay whole
+    assert a["param.weight.npy"].ndim == 1 and 0 < a["param.weight.npy"].size < 30000
+    lg = a["logits.npy"]
+    assert 0 < lg.size < 12000 and (np.diff(lg) > 0).all()  # sorted positions, no repeats
+    for f in a:
+        assert np.array_equal(a[f], np.load(tmp_path / "b" / f)), f
 
 
 def test_supervisor_rejects_multi_node_torchrun(monkeypatch):
