@@ -32,6 +32,7 @@
 // reduction has a fixed order (no float atomics).
 #include "common.h"
 #include "comm/xgmi.h"
+#include "kernels/handoff.h"
 
 namespace dpa {
 namespace bnh {
@@ -135,42 +136,9 @@ __device__ __forceinline__ void row_range(long long M, long long& r0, long long&
   r1 = r0 + per < M ? r0 + per : M;
 }
 
-// Write-through hand-off (MI355X_MICROARCH.md "Valid forms", row 1): partial rows
-// stored with agent-scope relaxed atomic stores (sc1, past the XCD's L2) and read
-// back with agent-scope atomic loads, so the ticket needs no release / acquire
-// fence -- an agent release writes back the whole L2 of the XCD, once per
-// workgroup.  g_handoff_wt (bn_nhwc.set_handoff) = 0 restores the fenced form.
-__device__ __forceinline__ void st_wt(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_wt(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Last-arriver election over `n` workgroups: fenced (wt = 0: agent-scope release /
-// acquire around the ticket) or write-through (wt = 1: the rows were stored sc1).
-__device__ __forceinline__ bool ticket_last(unsigned* ticket, int n, int* s_flag, int wt) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave: its partial-row stores are done
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (!wt) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = t == (unsigned)n - 1;
-    *s_flag = last;
-    if (last) {
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next launch
-      if (!wt) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    }
-  }
-  __syncthreads();
-  return *s_flag != 0;
-}
+// The statistics trees hand their partial rows over write-through (kernels/handoff.h:
+// st_wt / ld_wt, last_arriver); g_handoff_wt (bn_nhwc.set_handoff) = 0 restores the fenced
+// form (plain stores, release / acquire around the ticket).
 
 // dst[t] = sum_{g < n} src[g*W + t], W % 4 == 0, fixed order.  Lanes load
 // 16-B column vectors; the RG = THR/(W/4) row groups of the block each sum
@@ -235,7 +203,7 @@ __device__ bool chunk_reduce(float* __restrict__ part, unsigned* __restrict__ ti
   }
   const int grp = blockIdx.x / G1;
   const int gsz = min(G1, Gr - grp * G1);
-  if (!ticket_last(tickets + y * NG + grp, gsz, s_flag, wt)) return false;
+  if (!last_arriver(tickets + y * NG + grp, (unsigned)gsz, s_flag, wt != 0)) return false;
   if (NG == 1) {
     if (xs.active() && threadIdx.x == 0) *tk = xgmi::xsite_ticket(xs, y);
     sum_rows(p1, gsz, W, red, scr, wt, 0);
@@ -243,7 +211,7 @@ __device__ bool chunk_reduce(float* __restrict__ part, unsigned* __restrict__ ti
     return true;
   }
   sum_rows(p1 + (size_t)grp * G1 * W, gsz, W, p2 + (size_t)grp * W, scr, wt, wt);
-  if (!ticket_last(tickets + Gc * NG + y, NG, s_flag, wt)) return false;
+  if (!last_arriver(tickets + Gc * NG + y, (unsigned)NG, s_flag, wt != 0)) return false;
   if (xs.active() && threadIdx.x == 0) *tk = xgmi::xsite_ticket(xs, y);
   sum_rows(p2, NG, W, red, scr, wt, 0);
   __syncthreads();

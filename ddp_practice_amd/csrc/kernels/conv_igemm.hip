@@ -24,42 +24,14 @@
 //   * XCD-aware workgroup order (the channel tiles of one pixel tile share an L2);
 //   * the pixel tile's im2col addresses (n, ih0, iw0) are computed once per
 //     workgroup; padding / ragged M are zero-filled in the loader.
-#include <algorithm>
-#include <cstdlib>
-#include <type_traits>
-#include <vector>
-
-#include "common.h"
 #include "comm/xgmi.h"
+#include "kernels/conv_igemm.h"
 
 namespace dpa {
 namespace igemm {
 
-constexpr int THR = 256;
 constexpr int BM = 128;  // pixels per workgroup
-constexpr int BK = 64;   // reduction elements per K-step
 constexpr int SHIFT_OFF = 4;  // stats layout of bn_nhwc.hip: [2C] = rows, shift at [2C+4 ...)
-
-struct Geom {
-  int N, H, W, C, OH, OW, K, R, S, stride, pad;
-  long long M;  // N*OH*OW
-  int accumulate = 0;  // conv_fwd: y += conv(x, w) (a residual gradient already in y)
-  long long cls_rows = 0;  // MODE_S2T: pixel tiles per output parity class
-  const void* aux = nullptr;  // conv_fwd epilogue: y[n][oh][ow] += aux[n][oh/2][ow/2] at even (oh, ow)
-};
-
-// Loader modes of the implicit-GEMM kernels:
-//   MODE_GEN  one filter tap x 64 input channels per K-step (C % 64 == 0);
-//   MODE_STEM the 7x7 / stride-2 stem on a 4-channel (3 + one zero) NHWC image: K is
-//             the flattened (r, s, c) space padded to 8 x 8 x 4 = 256 (4 K-steps), a
-//             16-B chunk is two horizontally adjacent taps x 4 channels (two 8-B loads);
-//             the packed filter is [K][8][8][4] with zeros in the padding;
-//   MODE_S2T  the data gradient of a 3x3 / stride-2 / pad-1 conv (a transposed conv):
-//             dx is split by output parity (py, px) into four stride-1 sub-convolutions
-//             of dy with 1, 2, 2 and 4 of the taps -- no zero-inserted dy, no wasted MFMA
-//             -- each written with stride 2 into dx; filter = the flipped transpose.
-constexpr int MODE_GEN = 0, MODE_STEM = 1, MODE_S2T = 2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * BK + ((chunk ^ (row & 7)) << 3); }
 
@@ -104,31 +76,6 @@ struct BwdStatArgs {
   const float* beta = nullptr;
 };
 
-// Hand-off without fences (MI355X_MICROARCH.md "valid forms"): partial rows are
-// written with agent-scope relaxed atomic stores (write-through past the XCD's L2),
-// every wave drains its stores, one relaxed ticket per workgroup; the last arriver
-// reads the rows with agent-scope atomic loads.  No release fence: that would write
-// back the whole L2 (the conv output is dirty in it) once per workgroup.
-__device__ __forceinline__ void st_wt(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float ld_wt(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ bool last_arriver(unsigned* ticket, unsigned n, int* s_flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's write-through stores are done
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = t == n - 1;
-    *s_flag = last;
-    if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-  }
-  __syncthreads();
-  return *s_flag != 0;
-}
-
 // dst[0, W) = sum over rows g < n of src[g*W + .] in row order (W = 2*BN <= 256 floats;
 // src read with write-through loads; dst written write-through when `wt`): lane owns a
 // column, THR/W row groups, combined in group order via scr
@@ -159,6 +106,191 @@ __device__ __forceinline__ void sum_rows(const float* __restrict__ src, int n, f
   __syncthreads();
 }
 
+// ---------------------------------------------------------------------------
+// The tile epilogue of conv_fwd_kernel and conv_glds_kernel, and the statistics tree they
+// share with stat_tree_kernel.  A workgroup of NT threads holds a BPX-pixel x BN-channel
+// tile: lane (fr, fq) of a wave holds channels cw + 16a + 4fq + j of pixel pw + 16b + fr.
+// The rounded tile goes through LDS ([pixel][channel], rows padded by 16 B: the 8-byte
+// writes of a 16-pixel column are conflict-free) and leaves as whole 16-B chunks,
+// consecutive lanes along a pixel's channels (full rows per store).
+template <int BN>
+struct Epi {
+  static constexpr int RS = BN + 8;   // LDS row stride (elements)
+  static constexpr int CPR = BN / 8;  // 16-B chunks per pixel row
+};
+
+// accumulators -> the LDS tile (cw, pw: this wave's first channel / pixel of the tile)
+template <typename T, int BN, int CT, int PT>
+__device__ __forceinline__ void stage_tile(T* tile, const f32x4 (&acc)[CT][PT], int cw, int pw, int fr, int fq) {
+#pragma unroll
+  for (int a = 0; a < CT; ++a) {
+    const int cl = cw + a * 16 + 4 * fq;
+#pragma unroll
+    for (int b = 0; b < PT; ++b) {
+      const int pl = pw + b * 16 + fr;
+      T v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = Cvt<T>::from_f(acc[a][b][j]);
+      *reinterpret_cast<u16x4*>(tile + pl * Epi<BN>::RS + cl) = *reinterpret_cast<const u16x4*>(v);
+    }
+  }
+}
+
+// Output stores: whole 16-B chunks, consecutive lanes along a pixel's channels;
+// y (+)= tile (+ aux at the even pixels), summed in fp32, rounded once.  MODE_S2T writes
+// parity class (py, px) with stride 2.  OLDPRE: the accumulated-onto chunk of pass `it` was
+// prefetched by the kernel (old_of(it)) instead of being read here; stored(it, raw) sees
+// every stored chunk (the BN-backward sums of conv_glds_kernel).
+template <typename T, int BPX, int BN, int NT, int MODE, bool OLDPRE, typename OldFn, typename StoredFn>
+__device__ __forceinline__ void store_tile(const T* tile, T* __restrict__ y, const Geom& g, long long p0, int k0,
+                                           int py, int px, OldFn&& old_of, StoredFn&& stored) {
+  constexpr int RS = Epi<BN>::RS, CPR = Epi<BN>::CPR, RPI = NT / CPR;  // RPI: pixel rows per pass
+  const int tid = threadIdx.x, ch = tid % CPR;
+  const T* aux = reinterpret_cast<const T*>(g.aux);
+#pragma unroll
+  for (int it = 0; it < BPX / RPI; ++it) {
+    const int pl = it * RPI + tid / CPR;
+    const long long p = p0 + pl;
+    if (p < g.M) {
+      long long op = p;  // output pixel
+      int oh = 0, ow = 0, n = 0;
+      if (MODE == MODE_S2T || aux != nullptr) {
+        ow = (int)(p % g.OW);
+        const long long t = p / g.OW;
+        oh = (int)(t % g.OH);
+        n = (int)(t / g.OH);
+      }
+      if constexpr (MODE == MODE_S2T) op = ((long long)n * (2 * g.OH) + 2 * oh + py) * (2 * g.OW) + 2 * ow + px;
+      f32x4* dst = reinterpret_cast<f32x4*>(y + op * g.K + k0 + ch * 8);
+      f32x4 raw = *reinterpret_cast<const f32x4*>(tile + pl * RS + ch * 8);
+      const bool add_aux = aux != nullptr && !(oh & 1) && !(ow & 1);
+      if (g.accumulate || add_aux) {
+        f32x4 old = {0.f, 0.f, 0.f, 0.f}, ax = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (OLDPRE) old = old_of(it);
+        else if (g.accumulate) old = *dst;
+        if (add_aux)
+          ax = *reinterpret_cast<const f32x4*>(
+              aux + (((long long)n * (g.OH >> 1) + (oh >> 1)) * (g.OW >> 1) + (ow >> 1)) * g.K + k0 + ch * 8);
+        const T* a = reinterpret_cast<const T*>(&old);
+        const T* e = reinterpret_cast<const T*>(&ax);
+        T* b = reinterpret_cast<T*>(&raw);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          b[j] = Cvt<T>::from_f(Cvt<T>::to_f(a[j]) + Cvt<T>::to_f(e[j]) + Cvt<T>::to_f(b[j]));
+      }
+      *dst = raw;
+      stored(it, raw);
+    }
+  }
+}
+
+// Each lane's sums of its fixed 8-channel chunk over its rows of the tile: the rounded
+// values around the shift sh (the running mean), rows past the ragged end masked out
+template <typename T, int BPX, int BN, int NT>
+__device__ __forceinline__ void tile_col_sums(const T* tile, int plast, const float (&sh)[8], float (&s1)[8],
+                                              float (&s2)[8]) {
+  constexpr int RS = Epi<BN>::RS, CPR = Epi<BN>::CPR, RPI = NT / CPR;
+  const int tid = threadIdx.x, ch = tid % CPR;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
+  // unconditional reads of clamped rows (a per-row guard was a branch + wait per row)
+  f32x4 raw[BPX / RPI];
+#pragma unroll
+  for (int it = 0; it < BPX / RPI; ++it)
+    raw[it] = *reinterpret_cast<const f32x4*>(tile + min(it * RPI + tid / CPR, plast) * RS + ch * 8);
+#pragma unroll
+  for (int it = 0; it < BPX / RPI; ++it) {
+    const float m = it * RPI + tid / CPR <= plast ? 1.f : 0.f;
+    const T* e = reinterpret_cast<const T*>(&raw[it]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d = (Cvt<T>::to_f(e[j]) - sh[j]) * m;
+      s1[j] += d;
+      s2[j] = fmaf(d, d, s2[j]);
+    }
+  }
+}
+
+// The per-lane column sums -> red[wave][2][BN]: xor-reduced over the lanes of a wave that
+// share the chunk (the row bits of the lane index), then an LDS-only barrier:
+// __syncthreads() is a workgroup fence whose vmcnt(0) would wait here for the whole output
+// tile's stores to drain (~30 us on a 56x56 x 256 conv)
+template <int BN>
+__device__ __forceinline__ void reduce_cols(float (&s1)[8], float (&s2)[8], float (*red)[2][BN]) {
+  constexpr int CPR = Epi<BN>::CPR;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ch = tid % CPR;
+#pragma unroll
+  for (int o = CPR; o < 64; o <<= 1)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      s1[j] += __shfl_xor(s1[j], o);
+      s2[j] += __shfl_xor(s2[j], o);
+    }
+  if (lane < CPR)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      red[wave][0][ch * 8 + j] = s1[j];
+      red[wave][1][ch * 8 + j] = s2[j];
+    }
+  lds_barrier();
+}
+
+// red summed over the NW waves in wave order -> this pixel tile's level-1 row: plain stores
+// (the tree runs in a launch after this one) or write-through (the in-launch tree)
+template <int BN, int NW>
+__device__ __forceinline__ void write_level1(const float (*red)[2][BN], float* row, bool wt) {
+  for (int t = threadIdx.x; t < 2 * BN; t += 64 * NW) {
+    const int q = t / BN, c = t % BN;
+    float v = red[0][q][c];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v += red[w][q][c];
+    if (wt) st_wt(row + t, v); else row[t] = v;
+  }
+}
+
+// The tree above the level-1 rows of channel tile bn (THR threads; rows pixel tiles in NG
+// groups of G1).  Level 2: this workgroup sums group grp's gsz rows into the group's level-2
+// row and is ticketed; true in the last of the channel tile's NG arrivals.
+struct Tree {
+  float *lvl1, *lvl2;  // this channel tile's level-1 / level-2 rows
+  int NG;
+  template <int BN>
+  __device__ __forceinline__ static Tree of(const StatArgs& sa, int nct, int bn, long long rows) {
+    const int NG = (int)((rows + G1 - 1) / G1);
+    return {sa.part + (long long)bn * rows * (2 * BN),
+            sa.part + (long long)nct * rows * (2 * BN) + (long long)bn * NG * (2 * BN), NG};
+  }
+};
+template <int BN>
+__device__ __forceinline__ bool tree_level2(const StatArgs& sa, const Tree& t, int nct, int bn, int grp, int gsz,
+                                            float* scr, int* s_flag) {
+  sum_rows<2 * BN>(t.lvl1 + (long long)grp * G1 * (2 * BN), gsz, t.lvl2 + (long long)grp * (2 * BN), scr, true);
+  return last_arriver(sa.tickets + nct * t.NG + bn, (unsigned)t.NG, s_flag);
+}
+// tot = [sum | sumsq] of channel tile bn -> the final statistics [s1 | s2 | count | shift]
+template <int BN>
+__device__ __forceinline__ void write_stats(const StatArgs& sa, int K, int bn, const float* tot, float count) {
+  const int k0 = bn * BN, tid = threadIdx.x;
+  for (int t = tid; t < BN; t += THR) {
+    sa.stats[k0 + t] = tot[t];
+    sa.stats[K + k0 + t] = tot[BN + t];
+    sa.stats[2 * K + SHIFT_OFF + k0 + t] = sa.shift[k0 + t];
+  }
+  if (bn == 0 && tid == 0) {
+    sa.stats[2 * K] = count;
+    if (sa.nbt != nullptr) sa.nbt[0] = sa.nbt[0] + 1;
+  }
+}
+// The in-launch tree of a conv workgroup that was the last of its level-1 group
+template <int BN>
+__device__ __forceinline__ void tree_in_launch(const StatArgs& sa, const Geom& g, int nct, int bn, long long rows,
+                                               int grp, int gsz, float* scr, float* tot, int* s_flag) {
+  const Tree t = Tree::of<BN>(sa, nct, bn, rows);
+  if (!tree_level2<BN>(sa, t, nct, bn, grp, gsz, scr, s_flag)) return;
+  sum_rows<2 * BN>(t.lvl2, t.NG, tot, scr, false);
+  write_stats<BN>(sa, g.K, bn, tot, (float)g.M);
+}
+
 // slab: [gridDim(pixel tiles)][2][K] partial statistics (null: none)
 template <typename T, int BN, int MODE = MODE_GEN>
 __global__ void __launch_bounds__(THR)
@@ -174,12 +306,7 @@ conv_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w, T* __restrict_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wp = wave & 1, wc = wave >> 1;  // pixel half, channel half
   const int nct = g.K / BN;
-  // XCD-aware tile order: the hardware deals workgroup i to XCD i % 8; remap so that
-  // consecutive logical tiles -- the nct channel tiles of one pixel tile, which read the
-  // same activation rows -- run on one XCD and share its L2 (bijective for any grid)
-  const unsigned nwg = gridDim.x, hw = blockIdx.x;
-  const unsigned q8 = nwg / 8, r8 = nwg % 8, xcd = hw % 8, slot = hw / 8;
-  const unsigned lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const unsigned lid = xcd_tile();  // the nct channel tiles of one pixel tile share an L2
   const long long bm_all = lid / nct;
   const int bn = (int)(lid % nct);
   int cls = 0;  // MODE_S2T: output parity class (py, px)
@@ -306,156 +433,45 @@ conv_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w, T* __restrict_
     if (kt + 1 < KT) lstore(buf ^ 1);
     __syncthreads();
   }
-  // epilogue: lane holds channels k0 + wc*BN/2 + 16a + 4fq + j of pixel p0 + wp*64 + 16b + fr.
-  // The rounded tile goes through LDS ([pixel][channel], rows padded by 16 B: the
-  // 8-byte writes of a 16-pixel column are conflict-free) and leaves as whole 16-B
-  // chunks, consecutive lanes along a pixel's channels (full rows per store).
-  constexpr int RS = BN + 8;  // LDS row stride (elements)
+  // epilogue: lane holds channels k0 + wc*BN/2 + 16a + 4fq + j of pixel p0 + wp*64 + 16b + fr
   T* tile = lds[0];
-#pragma unroll
-  for (int a = 0; a < CT; ++a) {
-    const int cl = wc * (BN / 2) + a * 16 + 4 * fq;
-#pragma unroll
-    for (int b = 0; b < PT; ++b) {
-      const int pl = wp * 64 + b * 16 + fr;
-      T v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = Cvt<T>::from_f(acc[a][b][j]);
-      *reinterpret_cast<u16x4*>(tile + pl * RS + cl) = *reinterpret_cast<const u16x4*>(v);
-    }
-  }
+  stage_tile<T, BN>(tile, acc, wc * (BN / 2), wp * 64, fr, fq);
   __syncthreads();
   // With statistics, each lane first sums its fixed 8-channel chunk over its rows of
   // the tile (the rounded values, around the running mean) and the workgroup's partial
   // row goes out (write-through) and is ticketed BEFORE the output stores are issued:
   // the ticket's store drain then never waits for the output tile.
-  constexpr int CPR = BN / 8;        // 16-B chunks per pixel row
-  constexpr int RPI = THR / CPR;     // pixel rows per pass
   const bool stats = sa.part != nullptr;
-  const int ch = tid % CPR;
-  // output stores: whole 16-B chunks, consecutive lanes along a pixel's channels
-  const T* aux = reinterpret_cast<const T*>(g.aux);
-  auto store_tile = [&]() {
-#pragma unroll
-    for (int it = 0; it < BM / RPI; ++it) {
-      const int pl = it * RPI + tid / CPR;
-      const long long p = p0 + pl;
-      if (p < g.M) {
-        long long op = p;  // output pixel
-        int oh = 0, ow = 0, n = 0;
-        if (MODE == MODE_S2T || aux != nullptr) {
-          ow = (int)(p % g.OW);
-          const long long t = p / g.OW;
-          oh = (int)(t % g.OH);
-          n = (int)(t / g.OH);
-        }
-        if constexpr (MODE == MODE_S2T) op = ((long long)n * (2 * g.OH) + 2 * oh + py) * (2 * g.OW) + 2 * ow + px;
-        f32x4* dst = reinterpret_cast<f32x4*>(y + op * g.K + k0 + ch * 8);
-        f32x4 raw = *reinterpret_cast<const f32x4*>(tile + pl * RS + ch * 8);
-        const bool add_aux = aux != nullptr && !(oh & 1) && !(ow & 1);
-        if (g.accumulate || add_aux) {  // y (+)= tile (+ aux), summed in fp32, rounded once
-          f32x4 old = {0.f, 0.f, 0.f, 0.f}, ax = {0.f, 0.f, 0.f, 0.f};
-          if (g.accumulate) old = *dst;
-          if (add_aux)
-            ax = *reinterpret_cast<const f32x4*>(
-                aux + (((long long)n * (g.OH >> 1) + (oh >> 1)) * (g.OW >> 1) + (ow >> 1)) * g.K + k0 + ch * 8);
-          const T* a = reinterpret_cast<const T*>(&old);
-          const T* e = reinterpret_cast<const T*>(&ax);
-          T* b = reinterpret_cast<T*>(&raw);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            b[j] = Cvt<T>::from_f(Cvt<T>::to_f(a[j]) + Cvt<T>::to_f(e[j]) + Cvt<T>::to_f(b[j]));
-        }
-        *dst = raw;
-      }
-    }
+  auto store = [&]() {
+    store_tile<T, BM, BN, THR, MODE, false>(tile, y, g, p0, k0, py, px, [](int) { return f32x4{0.f, 0.f, 0.f, 0.f}; },
+                                            [](int, const f32x4&) {});
   };
   // Without statistics, or with the tree deferred to stat_tree_kernel, the stores leave
   // first and drain while the sums are taken from the tile still in LDS (the barrier
   // after the sums is LDS-only: __syncthreads() would wait for the stores); with the
   // in-launch tree they follow the ticket, whose vmcnt(0) must not wait for the tile.
   const bool stores_first = !stats || sa.defer;
-  if (stores_first) store_tile();
+  if (stores_first) store();
   bool last1 = false;
   long long rows = 0;
-  int NG = 0, grp = 0, gsz = 0;
+  int grp = 0, gsz = 0;
   if (stats) {
-    float s1[8], s2[8], sh[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s1[j] = s2[j] = 0.f;
-      sh[j] = shp[j];
-    }
-    // unconditional reads of clamped rows (a per-row guard was a branch + wait per row)
-    const int plast = (int)min((long long)BM, g.M - p0) - 1;
-    f32x4 raw[BM / RPI];
-#pragma unroll
-    for (int it = 0; it < BM / RPI; ++it)
-      raw[it] = *reinterpret_cast<const f32x4*>(tile + min(it * RPI + tid / CPR, plast) * RS + ch * 8);
-#pragma unroll
-    for (int it = 0; it < BM / RPI; ++it) {
-      const float m = it * RPI + tid / CPR <= plast ? 1.f : 0.f;
-      const T* e = reinterpret_cast<const T*>(&raw[it]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float d = (Cvt<T>::to_f(e[j]) - sh[j]) * m;
-        s1[j] += d;
-        s2[j] = fmaf(d, d, s2[j]);
-      }
-    }
-    // lanes of one wave sharing the chunk: xor over the row bits of the lane index
-#pragma unroll
-    for (int o = CPR; o < 64; o <<= 1)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        s1[j] += __shfl_xor(s1[j], o);
-        s2[j] += __shfl_xor(s2[j], o);
-      }
-    if (lane < CPR)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        red[wave][0][ch * 8 + j] = s1[j];
-        red[wave][1][ch * 8 + j] = s2[j];
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    float s1[8], s2[8];
+    tile_col_sums<T, BM, BN, THR>(tile, (int)min((long long)BM, g.M - p0) - 1, shp, s1, s2);
+    reduce_cols<BN>(s1, s2, red);
     rows = (g.M + BM - 1) / BM;
-    NG = (int)((rows + G1 - 1) / G1);
     float* lvl1 = sa.part + (long long)bn * rows * (2 * BN);
-    if (sa.defer) {  // plain stores; the tree runs in stat_tree_kernel after this launch
-      for (int t = tid; t < 2 * BN; t += THR) {
-        const int q = t / BN, c = t % BN;
-        lvl1[bm * (2 * BN) + t] = red[0][q][c] + red[1][q][c] + red[2][q][c] + red[3][q][c];
-      }
-    } else {
-      for (int t = tid; t < 2 * BN; t += THR) {
-        const int q = t / BN, c = t % BN;
-        st_wt(lvl1 + bm * (2 * BN) + t, red[0][q][c] + red[1][q][c] + red[2][q][c] + red[3][q][c]);
-      }
+    write_level1<BN, 4>(red, lvl1 + bm * (2 * BN), !sa.defer);
+    if (!sa.defer) {
       grp = (int)(bm / G1);
       gsz = (int)min((long long)G1, rows - (long long)grp * G1);
-      last1 = last_arriver(sa.tickets + bn * NG + grp, (unsigned)gsz, &s_flag);
+      last1 = last_arriver(sa.tickets + bn * (int)((rows + G1 - 1) / G1) + grp, (unsigned)gsz, &s_flag);
     }
   }
-  if (!stores_first) store_tile();
+  if (!stores_first) store();
   if (!last1) return;
   __syncthreads();  // every lane is done with the tile: its LDS becomes the tree's scratch
-  float* scr = reinterpret_cast<float*>(lds[1]);
-  float* lvl1 = sa.part + (long long)bn * rows * (2 * BN);
-  float* lvl2 = sa.part + (long long)nct * rows * (2 * BN) + (long long)bn * NG * (2 * BN);
-  sum_rows<2 * BN>(lvl1 + (long long)grp * G1 * (2 * BN), gsz, lvl2 + (long long)grp * (2 * BN), scr, true);
-  if (!last_arriver(sa.tickets + nct * NG + bn, (unsigned)NG, &s_flag)) return;
-  float* tot = &red[0][0][0];
-  sum_rows<2 * BN>(lvl2, NG, tot, scr, false);
-  for (int t = tid; t < BN; t += THR) {
-    sa.stats[k0 + t] = tot[t];
-    sa.stats[g.K + k0 + t] = tot[BN + t];
-    sa.stats[2 * g.K + SHIFT_OFF + k0 + t] = sa.shift[k0 + t];
-  }
-  if (bn == 0 && tid == 0) {
-    sa.stats[2 * g.K] = (float)g.M;
-    if (sa.nbt != nullptr) sa.nbt[0] = sa.nbt[0] + 1;
-  }
+  tree_in_launch<BN>(sa, g, nct, bn, rows, grp, gsz, reinterpret_cast<float*>(lds[1]), &red[0][0][0], &s_flag);
 }
 
 // ---------------------------------------------------------------------------
@@ -496,19 +512,6 @@ struct G1x1Lds {
   static constexpr int BYTES = BWC + 4 * BN * 4;
 };
 
-// one global_load_lds_dwordx4: 16 B per lane from `src` (per lane) to dst + 16 * lane (dst
-// wave-uniform).  A non-template device function: called directly inside the kernel
-// template, hipcc's host pass fails to instantiate it and emits no launch stub (undefined
-// __device_stub__ at load time).
-typedef __attribute__((address_space(3))) void* lds_vptr;
-__device__ __forceinline__ void glds16(const void* src, void* dst) {
-  __builtin_amdgcn_global_load_lds(src, (lds_vptr)dst, 16, 0, 0);
-}
-
-// 16 zero bytes: the LDS-DMA source of padding taps and out-of-range rows (a DMA cannot
-// zero-fill; its per-lane source address can point here instead)
-__device__ __attribute__((aligned(16))) unsigned char g_zero16[16] = {0};
-
 // NS = 3 | 4 (DPA_GLDS_STAGES): three or four LDS buffers, NS - 1 tiles in flight across every barrier --
 // the wait is a counted vmcnt (this wave's DMAs of the newest tile stay outstanding) and the
 // barrier a raw s_barrier (__syncthreads() would add vmcnt(0)); one workgroup per CU (96 or 128 KB).
@@ -541,10 +544,7 @@ conv_glds_kernel(const T* __restrict__ x, const T* __restrict__ w, T* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wp = wave % NWP, wc = wave / NWP;
   const int nct = g.K / BN;
-  // XCD-aware order (as conv_fwd_kernel): the channel tiles of one pixel tile share an L2
-  const unsigned nwg = gridDim.x, hw = blockIdx.x;
-  const unsigned q8 = nwg / 8, r8 = nwg % 8, xcd = hw % 8, slot = hw / 8;
-  const unsigned lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+  const unsigned lid = xcd_tile();  // the nct channel tiles of one pixel tile share an L2
   const long long bm = lid / nct;
   const int bn = (int)(lid % nct);
   const long long p0 = bm * BP;
@@ -683,32 +683,13 @@ conv_glds_kernel(const T* __restrict__ x, const T* __restrict__ w, T* __restrict
     if constexpr (NS >= 3) buf = buf == NS - 1 ? 0 : buf + 1;
   }
   __syncthreads();  // the last tile is read: the buffers become the epilogue's tile
-  // ---- epilogue (conv_fwd_kernel's, for a BP-pixel tile) ----
-  constexpr int RS = L::RS;
+  // ---- epilogue (the shared pieces, for a BP-pixel tile) ----
   T* tile = lds;
   float(*red)[2][BN] = reinterpret_cast<float(*)[2][BN]>(smem + L::RED);
-  auto wave_sum = [&](int t) {  // column t of [2][BN] summed over the waves, in wave order
-    const int q = t / BN, c = t % BN;
-    float v = red[0][q][c];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) v += red[w][q][c];
-    return v;
-  };
   int* s_flag = reinterpret_cast<int*>(smem + L::FLAG);
   float* scr = reinterpret_cast<float*>(smem + L::SCR);
   const float* shl = reinterpret_cast<const float*>(smem + L::SHIFT);
-#pragma unroll
-  for (int a = 0; a < CT; ++a) {
-    const int cl = wc * (BN / NWC) + a * 16 + 4 * fq;
-#pragma unroll
-    for (int b = 0; b < PT; ++b) {
-      const int pl = wp * (BP / NWP) + b * 16 + fr;
-      T v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = Cvt<T>::from_f(acc[a][b][j]);
-      *reinterpret_cast<u16x4*>(tile + pl * RS + cl) = *reinterpret_cast<const u16x4*>(v);
-    }
-  }
+  stage_tile<T, BN>(tile, acc, wc * (BN / NWC), wp * (BP / NWP), fr, fq);
   __syncthreads();
   const bool stats = BS == BS_NONE && sa.part != nullptr;
   // BS: this lane's 8 channels' BN constants, and its running sums of dz, dz * xhat
@@ -726,156 +707,60 @@ conv_glds_kernel(const T* __restrict__ x, const T* __restrict__ w, T* __restrict
       bs1[j] = bs2[j] = 0.f;
     }
   }
-  // output stores: whole 16-B chunks, consecutive lanes along a pixel's channels
-  const T* aux = reinterpret_cast<const T*>(g.aux);
-  auto store_tile = [&]() {
+  auto store = [&]() {
+    store_tile<T, BP, BN, NT, MODE_GEN, BS == BS_Y>(
+        tile, y, g, p0, k0, 0, 0, [&](int it) { return bor[BS == BS_Y ? it : 0]; },  // prefetched with tile 0
+        [&](int it, const f32x4& raw) {
+          if constexpr (BS != BS_NONE) {  // the BN backward sums of the stored (rounded) gradient
+            const T* d = reinterpret_cast<const T*>(&raw);
+            const T* xv = reinterpret_cast<const T*>(&bxr[it]);
+            const T* yv = reinterpret_cast<const T*>(&byr[it]);
 #pragma unroll
-    for (int it = 0; it < BP / RPI; ++it) {
-      const int pl = it * RPI + tid / CPR;
-      const long long p = p0 + pl;
-      if (p < g.M) {
-        f32x4* dst = reinterpret_cast<f32x4*>(y + p * g.K + k0 + ch * 8);
-        f32x4 raw = *reinterpret_cast<const f32x4*>(tile + pl * RS + ch * 8);
-        int oh = 0, ow = 0, n = 0;
-        if (aux != nullptr) {
-          ow = (int)(p % g.OW);
-          const long long t = p / g.OW;
-          oh = (int)(t % g.OH);
-          n = (int)(t / g.OH);
-        }
-        const bool add_aux = aux != nullptr && !(oh & 1) && !(ow & 1);
-        if (g.accumulate || add_aux) {
-          f32x4 old = {0.f, 0.f, 0.f, 0.f}, ax = {0.f, 0.f, 0.f, 0.f};
-          if constexpr (BS == BS_Y) old = bor[it];  // prefetched with tile 0
-          else if (g.accumulate) old = *dst;
-          if (add_aux)
-            ax = *reinterpret_cast<const f32x4*>(
-                aux + (((long long)n * (g.OH >> 1) + (oh >> 1)) * (g.OW >> 1) + (ow >> 1)) * g.K + k0 + ch * 8);
-          const T* a = reinterpret_cast<const T*>(&old);
-          const T* e = reinterpret_cast<const T*>(&ax);
-          T* b = reinterpret_cast<T*>(&raw);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            b[j] = Cvt<T>::from_f(Cvt<T>::to_f(a[j]) + Cvt<T>::to_f(e[j]) + Cvt<T>::to_f(b[j]));
-        }
-        *dst = raw;
-        if constexpr (BS != BS_NONE) {  // the BN backward sums of the stored (rounded) gradient
-          const T* d = reinterpret_cast<const T*>(&raw);
-          const T* xv = reinterpret_cast<const T*>(&bxr[it]);
-          const T* yv = reinterpret_cast<const T*>(&byr[it]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float xf = Cvt<T>::to_f(xv[j]);
-            const bool on = BS == BS_Y ? Cvt<T>::to_f(yv[j]) > 0.f : fmaf(xf, bsc[j], bsh[j]) > 0.f;
-            const float z = on ? Cvt<T>::to_f(d[j]) : 0.f;
-            bs1[j] += z;
-            bs2[j] = fmaf(z, (xf - bmu[j]) * bis[j], bs2[j]);
+            for (int j = 0; j < 8; ++j) {
+              const float xf = Cvt<T>::to_f(xv[j]);
+              const bool on = BS == BS_Y ? Cvt<T>::to_f(yv[j]) > 0.f : fmaf(xf, bsc[j], bsh[j]) > 0.f;
+              const float z = on ? Cvt<T>::to_f(d[j]) : 0.f;
+              bs1[j] += z;
+              bs2[j] = fmaf(z, (xf - bmu[j]) * bis[j], bs2[j]);
+            }
           }
-        }
-      }
-    }
+        });
   };
   // Without statistics, or with the tree deferred to stat_tree_kernel, the stores leave
   // first and drain while the sums are taken from the tile still in LDS; with the
   // in-launch tree they follow the ticket (its vmcnt(0) must not wait for the tile).
   const bool stores_first = !stats || sa.defer || !kInTree;
-  if (stores_first) store_tile();
-  if constexpr (BS != BS_NONE) {  // -> level-1 row of this pixel tile (stat_tree_kernel follows)
-#pragma unroll
-    for (int o = CPR; o < 64; o <<= 1)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        bs1[j] += __shfl_xor(bs1[j], o);
-        bs2[j] += __shfl_xor(bs2[j], o);
-      }
-    if (lane < CPR)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        red[wave][0][ch * 8 + j] = bs1[j];
-        red[wave][1][ch * 8 + j] = bs2[j];
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const long long nrows = (g.M + BP - 1) / BP;
-    float* lvl1 = sa.part + (long long)bn * nrows * (2 * BN);
-    for (int t = tid; t < 2 * BN; t += NT) lvl1[bm * (2 * BN) + t] = wave_sum(t);
+  if (stores_first) store();
+  // this pixel tile's level-1 row of channel tile bn
+  auto lvl1_row = [&](long long rows) { return sa.part + ((long long)bn * rows + bm) * (2 * BN); };
+  if constexpr (BS != BS_NONE) {  // -> level-1 row (stat_tree_kernel follows)
+    reduce_cols<BN>(bs1, bs2, red);
+    write_level1<BN, NW>(red, lvl1_row((g.M + BP - 1) / BP), false);
     return;
   }
   bool last1 = false;
   long long rows = 0;
-  int NG = 0, grp = 0, gsz = 0;
+  int grp = 0, gsz = 0;
   if (stats) {
+    rows = (g.M + BP - 1) / BP;
     float s1[8], s2[8], sh[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s1[j] = s2[j] = 0.f;
-      sh[j] = shl[ch * 8 + j];
-    }
-    // unconditional reads of clamped rows (a per-row guard was a branch + wait per row)
-    const int plast = (int)min((long long)BP, g.M - p0) - 1;
-    f32x4 raw[BP / RPI];
-#pragma unroll
-    for (int it = 0; it < BP / RPI; ++it)
-      raw[it] = *reinterpret_cast<const f32x4*>(tile + min(it * RPI + tid / CPR, plast) * RS + ch * 8);
-#pragma unroll
-    for (int it = 0; it < BP / RPI; ++it) {
-      const float m = it * RPI + tid / CPR <= plast ? 1.f : 0.f;
-      const T* e = reinterpret_cast<const T*>(&raw[it]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float d = (Cvt<T>::to_f(e[j]) - sh[j]) * m;
-        s1[j] += d;
-        s2[j] = fmaf(d, d, s2[j]);
-      }
-    }
-#pragma unroll
-    for (int o = CPR; o < 64; o <<= 1)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        s1[j] += __shfl_xor(s1[j], o);
-        s2[j] += __shfl_xor(s2[j], o);
-      }
-    if (lane < CPR)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        red[wave][0][ch * 8 + j] = s1[j];
-        red[wave][1][ch * 8 + j] = s2[j];
-      }
-    // LDS-only barrier: __syncthreads() is a workgroup fence whose vmcnt(0) would wait
-    // here for the whole output tile's stores to drain (~30 us on a 56x56 x 256 conv)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    rows = (g.M + BP - 1) / BP;
-    NG = (int)((rows + G1 - 1) / G1);
-    float* lvl1 = sa.part + (long long)bn * rows * (2 * BN);
-    if (sa.defer || !kInTree) {  // plain stores; the tree runs in stat_tree_kernel after this launch
-      for (int t = tid; t < 2 * BN; t += NT) lvl1[bm * (2 * BN) + t] = wave_sum(t);
-    } else {
-      for (int t = tid; t < 2 * BN; t += NT) st_wt(lvl1 + bm * (2 * BN) + t, wave_sum(t));
+    for (int j = 0; j < 8; ++j) sh[j] = shl[ch * 8 + j];
+    tile_col_sums<T, BP, BN, NT>(tile, (int)min((long long)BP, g.M - p0) - 1, sh, s1, s2);
+    reduce_cols<BN>(s1, s2, red);
+    const bool deferred = sa.defer || !kInTree;  // the tree runs in stat_tree_kernel after this launch
+    write_level1<BN, NW>(red, lvl1_row(rows), !deferred);
+    if (!deferred) {
       grp = (int)(bm / G1);
       gsz = (int)min((long long)G1, rows - (long long)grp * G1);
-      last1 = last_arriver(sa.tickets + bn * NG + grp, (unsigned)gsz, s_flag);
+      last1 = last_arriver(sa.tickets + bn * (int)((rows + G1 - 1) / G1) + grp, (unsigned)gsz, s_flag);
     }
   }
-  if (!stores_first) store_tile();
+  if (!stores_first) store();
   if (!last1) return;
   if constexpr (kInTree) {  // (wide tiles always defer: last1 is false there)
     __syncthreads();
-    float* lvl1 = sa.part + (long long)bn * rows * (2 * BN);
-    float* lvl2 = sa.part + (long long)nct * rows * (2 * BN) + (long long)bn * NG * (2 * BN);
-    sum_rows<2 * BN>(lvl1 + (long long)grp * G1 * (2 * BN), gsz, lvl2 + (long long)grp * (2 * BN), scr, true);
-    if (!last_arriver(sa.tickets + nct * NG + bn, (unsigned)NG, s_flag)) return;
-    float* tot = &red[0][0][0];
-    sum_rows<2 * BN>(lvl2, NG, tot, scr, false);
-    for (int t = tid; t < BN; t += NT) {
-      sa.stats[k0 + t] = tot[t];
-      sa.stats[g.K + k0 + t] = tot[BN + t];
-      sa.stats[2 * g.K + SHIFT_OFF + k0 + t] = sa.shift[k0 + t];
-    }
-    if (bn == 0 && tid == 0) {
-      sa.stats[2 * g.K] = (float)g.M;
-      if (sa.nbt != nullptr) sa.nbt[0] = sa.nbt[0] + 1;
-    }
+    tree_in_launch<BN>(sa, g, nct, bn, rows, grp, gsz, scr, &red[0][0][0], s_flag);
   }
 }
 
@@ -970,15 +855,13 @@ __global__ void __launch_bounds__(THR) stat_tree_kernel(StatArgs sa, long long M
   const int bn = (int)(blockIdx.x / NG), grp = (int)(blockIdx.x % NG);
   const int gsz = (int)min((long long)G1, rows - (long long)grp * G1);
   const int k0 = bn * BN, tid = threadIdx.x;
-  float* lvl1 = sa.part + (long long)bn * rows * (2 * BN);
-  float* lvl2 = sa.part + (long long)nct * rows * (2 * BN) + (long long)bn * NG * (2 * BN);
-  sum_rows<2 * BN>(lvl1 + (long long)grp * G1 * (2 * BN), gsz, lvl2 + (long long)grp * (2 * BN), scr, true);
-  if (!last_arriver(sa.tickets + nct * NG + bn, (unsigned)NG, &s_flag)) return;
+  const Tree tr = Tree::of<BN>(sa, nct, bn, rows);
+  if (!tree_level2<BN>(sa, tr, nct, bn, grp, gsz, scr, &s_flag)) return;
   // SyncBN: the nct finishers exchange their slices (ticket round trip behind the level-2 loads)
   const bool xon = sa.xs.active();
   unsigned long long tk = 0;
   if (xon && tid == 0) tk = xgmi::xsite_ticket(sa.xs, bn);
-  sum_rows<2 * BN>(lvl2, NG, tot, scr, false);
+  sum_rows<2 * BN>(tr.lvl2, NG, tot, scr, false);
   if (sa.bwd) {  // BN backward sums: out = [S1 | S2], dbeta = S1, dgamma = S2 (bn_nhwc layout)
     for (int t = tid; t < BN; t += THR) {
       sa.dbeta[k0 + t] = tot[t];  // this rank's (DDP averages them)
@@ -1002,448 +885,7 @@ __global__ void __launch_bounds__(THR) stat_tree_kernel(StatArgs sa, long long M
                                tk, bn, THR);
     if (bn == 0 && tid == 0) cnt[0] = tot[2 * BN];
   }
-  for (int t = tid; t < BN; t += THR) {
-    sa.stats[k0 + t] = tot[t];
-    sa.stats[K + k0 + t] = tot[BN + t];
-    sa.stats[2 * K + SHIFT_OFF + k0 + t] = sa.shift[k0 + t];
-  }
-  if (bn == 0 && tid == 0) {
-    sa.stats[2 * K] = cnt[0];
-    if (sa.nbt != nullptr) sa.nbt[0] = sa.nbt[0] + 1;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Weight gradient:  dW[k][r][s][c] = sum_p dy[p][k] * x[n][oh*st+r-pad][ow*st+s-pad][c]
-// GEMM M = Cout, N = R*S*C, reduction over the pixels p -- both operands are stored
-// pixel-major, so they are staged in LDS as [64 pixels][cols] rows and read TRANSPOSED
-// into the MFMA operands with ds_read_b64_tr_b16 (each 16-lane group: 4 pixel rows x
-// 16 columns; two reads make a lane's 8 consecutive pixels).  Row chunks are XOR-
-// swizzled by 2*f(row), f(row) = (row&3) | ((row>>1)&4): the 8 rows one 32-lane half
-// reads map to 8 distinct chunk pairs (conflict-free with 16 chunks per row).
-// Split over the pixels: S partial fp32 tiles -> wgrad_reduce_kernel, which also
-// writes the fp32 OIHW gradient directly (no separate layout/cast pass).
-typedef __attribute__((ext_vector_type(4))) short v4s;
-
-// With 8 chunks per row (128-B rows: 64-channel tiles) one 32-lane half reads rows
-// {0..3, 8..11} (+4, +32kk), the even ones in one bank half: their 4 chunk pairs must
-// differ, so the XOR there is 2*f8(row), f8 = bit 1 | bit 3 of the row (was 2*(row&3):
-// rows r and r+8 shared a pair, 2-way -- 1.6 conflict cycles per LDS instruction in the
-// 64-wide wgrad kernels, profiles/r3s2l_resnet50_pmc_pass1.txt).
-template <int CH>
-__device__ __forceinline__ int wswz_xor(int row) {
-  if constexpr (CH >= 16) return 2 * ((row & 3) | ((row >> 1) & 4));
-  return 2 * (((row >> 1) & 1) | ((row >> 2) & 2));
-}
-
-template <int CH>  // 16-B chunks per LDS row
-__device__ __forceinline__ int wswz(int row, int chunk) {
-  return row * CH * 8 + ((chunk ^ wswz_xor<CH>(row)) << 3);
-}
-
-template <typename T, int BM, int BN, int MODE = MODE_GEN>
-__global__ void __launch_bounds__(THR)
-conv_wgrad_kernel(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ slab, Geom g, int splits,
-                  long long pps) {
-  typedef typename MM<T>::frag frag;
-  constexpr int BP = 64;                 // pixels per K-step
-  constexpr int CHA = BM / 8, CHB = BN / 8;
-  constexpr int LA = BP * CHA / THR, LB = BP * CHB / THR;  // 16-B loads per thread
-  constexpr int MT = BM / 32, NT = BN / 32;
-  __shared__ __attribute__((aligned(16))) T lds[2][BP * (BM + BN)];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave & 1, wn = wave >> 1;
-  const int RSC = MODE == MODE_STEM ? 256 : g.R * g.S * g.C;  // stem: [8][8][4] padded columns
-  const int tm = g.K / BM, tn = RSC / BN, tiles = tm * tn;
-  const unsigned nwg = gridDim.x, hw = blockIdx.x;
-  const unsigned q8 = nwg / 8, r8 = nwg % 8, xcd = hw % 8, slot = hw / 8;
-  const unsigned lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-  const int sp = (int)(lid / tiles), tile = (int)(lid % tiles);
-  const int k0 = (tile / tn) * BM, n0 = (tile % tn) * BN;
-  const int rs = n0 / g.C, c0 = n0 - rs * g.C, fr_ = rs / g.S, fs_ = rs - fr_ * g.S;
-  const long long pa = sp * pps, pb = min(g.M, pa + pps);
-  const int steps = (int)((pb - pa + BP - 1) / BP);
-  f32x4 ra[LA], rb[LB];
-  auto gload = [&](int t) {
-    const long long pbase = pa + (long long)t * BP;
-#pragma unroll
-    for (int i = 0; i < LA; ++i) {
-      const int e = i * THR + tid, row = e / CHA, cc = e % CHA;
-      const long long p = pbase + row;
-      ra[i] = p < pb ? *reinterpret_cast<const f32x4*>(dy + p * g.K + k0 + cc * 8) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int i = 0; i < LB; ++i) {
-      const int e = i * THR + tid, row = e / CHB, cc = e % CHB;
-      const long long p = pbase + row;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (p < pb) {
-        const unsigned pu = (unsigned)p, q = pu / (unsigned)g.OW;  // M < 2^31 (host check)
-        const int ow = (int)(pu - q * (unsigned)g.OW);
-        const unsigned n = q / (unsigned)g.OH;
-        const int oh = (int)(q - n * (unsigned)g.OH);
-        if constexpr (MODE == MODE_STEM) {
-          // column n0 + 8cc: taps (r, s), (r, s + 1) of the [8][8][4] padded filter space
-          const int col = n0 + cc * 8, r = col >> 5, s = (col >> 2) & 7;
-          const int ih = oh * g.stride + r - g.pad, iw = ow * g.stride + s - g.pad;
-          const bool rok = r < 7 && (unsigned)ih < (unsigned)g.H;
-          const T* px_ = x + (((long long)n * g.H + ih) * g.W + iw) * 4;
-          f32x2 lo = {0.f, 0.f}, hi = {0.f, 0.f};
-          if (rok && (unsigned)iw < (unsigned)g.W) lo = *reinterpret_cast<const f32x2*>(px_);
-          if (rok && s + 1 < 7 && (unsigned)(iw + 1) < (unsigned)g.W) hi = *reinterpret_cast<const f32x2*>(px_ + 4);
-          v = f32x4{lo[0], lo[1], hi[0], hi[1]};
-        } else {
-          const int ih = oh * g.stride + fr_ - g.pad, iw = ow * g.stride + fs_ - g.pad;
-          if ((unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W)
-            v = *reinterpret_cast<const f32x4*>(x + (((long long)n * g.H + ih) * g.W + iw) * g.C + c0 + cc * 8);
-        }
-      }
-      rb[i] = v;
-    }
-  };
-  auto lstore = [&](int buf) {
-    T* A = lds[buf];
-    T* B = lds[buf] + BP * BM;
-#pragma unroll
-    for (int i = 0; i < LA; ++i) {
-      const int e = i * THR + tid;
-      *reinterpret_cast<f32x4*>(A + wswz<CHA>(e / CHA, e % CHA)) = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < LB; ++i) {
-      const int e = i * THR + tid;
-      *reinterpret_cast<f32x4*>(B + wswz<CHB>(e / CHB, e % CHB)) = rb[i];
-    }
-  };
-  // transposed fragment: 8 consecutive pixel rows (32kk + 8g .. +7) of column cb + (lane & 15)
-  const int grp = lane >> 4, gi = lane & 15, q = gi >> 2, pq = gi & 3;
-  auto trfrag = [&](const T* base, int kk, int cb, auto chtag) -> frag {
-    constexpr int CH = decltype(chtag)::value;
-    const int row = 32 * kk + 8 * grp + q, col = cb + 4 * pq;
-    const T* a0 = base + wswz<CH>(row, col >> 3) + (col & 7);
-    const T* a1 = base + wswz<CH>(row + 4, col >> 3) + (col & 7);
-    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)a0);
-    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)a1);
-    typedef __attribute__((ext_vector_type(8))) short v8s;
-    const v8s v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(frag, v);
-  };
-  f32x4 acc[MT][NT];
-#pragma unroll
-  for (int a = 0; a < MT; ++a)
-#pragma unroll
-    for (int b = 0; b < NT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (steps > 0) {
-    gload(0);
-    lstore(0);
-  }
-  __syncthreads();
-  for (int t = 0; t < steps; ++t) {
-    const int buf = t & 1;
-    if (t + 1 < steps) gload(t + 1);
-    const T* A = lds[buf];
-    const T* B = lds[buf] + BP * BM;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      frag fa[MT], fb[NT];
-#pragma unroll
-      for (int a = 0; a < MT; ++a)
-        fa[a] = trfrag(A, kk, wm * (BM / 2) + a * 16, std::integral_constant<int, CHA>{});
-#pragma unroll
-      for (int b = 0; b < NT; ++b)
-        fb[b] = trfrag(B, kk, wn * (BN / 2) + b * 16, std::integral_constant<int, CHB>{});
-#pragma unroll
-      for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int b = 0; b < NT; ++b) acc[a][b] = MM<T>::mma(fa[a], fb[b], acc[a][b]);
-    }
-    if (t + 1 < steps) lstore(buf ^ 1);
-    __syncthreads();
-  }
-  // partial tile: C[m = k][n = (r,s,c)]; lane: col n = lane & 15, rows 4*(lane>>4) + j
-  float* out = slab + (long long)sp * g.K * RSC;
-#pragma unroll
-  for (int a = 0; a < MT; ++a)
-#pragma unroll
-    for (int b = 0; b < NT; ++b)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int m = k0 + wm * (BM / 2) + a * 16 + 4 * grp + j, n = n0 + wn * (BN / 2) + b * 16 + gi;
-        out[(long long)m * RSC + n] = acc[a][b][j];
-      }
-}
-
-// The same weight gradient with both operand tiles staged global -> LDS by LDS-DMA
-// (MODE_GEN): no VGPR staging and no ds_write_b128 pass (the register-staged loop pays
-// ~13 LDS cycles per KiB written).  A wave-instruction fills 64/CH whole rows of the
-// [64 pixels][CH chunks] image, lane l row l / CH at slot l % CH; the wswz swizzle goes on
-// the per-lane source address (logical chunk = slot ^ xor(row)); padding taps and pixels
-// past the split's end read a 16-B zero page instead of being zero-filled by the loader.
-// One barrier per 64-pixel step: wait the landed step (vmcnt(0)) + barrier, issue step
-// t+1 into the other buffer, MFMA on step t (as conv_glds_kernel).
-
-// NWM x NWN waves (default 2 x 2; 2 x 4 = 8 waves, DPA_WGRAD_WAVES=8: the second wave on
-// every SIMD hides the other's transposed-read waits, as the forward's 8-wave tiles do).
-// FIX (DPA_WGRAD_FIXUP_MAXSP, opt-in): the split-K reduction in this launch -- partial
-// tiles stored write-through, one ticket per output tile, and the tile's last arriver sums
-// the splits in split order and writes the fp32 OIHW gradient (no wgrad_reduce launch).
-template <typename T, int BM, int BN, int NWM = 2, int NWN = 2, bool FIX = false>
-__global__ void __launch_bounds__(64 * NWM * NWN)
-conv_wgrad_glds_kernel(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ slab, Geom g,
-                       int splits, long long pps, float* __restrict__ grad, unsigned* __restrict__ tickets) {
-  typedef typename MM<T>::frag frag;
-  constexpr int BP = 64;
-  constexpr int CHA = BM / 8, CHB = BN / 8;
-  constexpr int NW = NWM * NWN;
-  constexpr int IA = CHA / NW, IB = CHB / NW;  // wave-instructions per wave per step
-  constexpr int MT = BM / (16 * NWM), NT = BN / (16 * NWN);
-  static_assert(IA >= 1 && IB >= 1 && IA * NW == CHA && IB * NW == CHB && MT >= 1 && NT >= 1, "tile / waves");
-  constexpr int STAGE = BP * (BM + BN);
-  __shared__ __attribute__((aligned(16))) T lds[2 * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave % NWM, wn = wave / NWM;
-  const int RSC = g.R * g.S * g.C;
-  const int tm = g.K / BM, tn = RSC / BN, tiles = tm * tn;
-  const unsigned nwg = gridDim.x, hw = blockIdx.x;
-  const unsigned q8 = nwg / 8, r8 = nwg % 8, xcd = hw % 8, slot = hw / 8;
-  const unsigned lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-  const int sp = (int)(lid / tiles), tile = (int)(lid % tiles);
-  const int k0 = (tile / tn) * BM, n0 = (tile % tn) * BN;
-  const int rs = n0 / g.C, c0 = n0 - rs * g.C, fr_ = rs / g.S, fs_ = rs - fr_ * g.S;
-  const long long pa = sp * pps, pb = min(g.M, pa + pps);
-  const int steps = (int)((pb - pa + BP - 1) / BP);
-  const bool plain = g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0;  // x rows = pixels
-  // this lane's rows and source chunks (row = (i*4 + wave) * (64/CH) + lane / CH)
-  const int ra = lane / CHA, rb = lane / CHB;
-  auto issue = [&](int t, int buf) {
-    T* A = lds + buf * STAGE;
-    T* B = A + BP * BM;
-    const long long pbase = pa + (long long)t * BP;
-#pragma unroll
-    for (int i = 0; i < IA; ++i) {
-      const int row = (i * NW + wave) * (64 / CHA) + ra;
-      const int ck = (lane % CHA) ^ wswz_xor<CHA>(row);
-      const long long p = pbase + row;
-      const void* src = p < pb ? (const void*)(dy + p * g.K + k0 + ck * 8) : (const void*)g_zero16;
-      glds16(src, A + (i * NW + wave) * (64 / CHA) * BM);
-    }
-#pragma unroll
-    for (int i = 0; i < IB; ++i) {
-      const int row = (i * NW + wave) * (64 / CHB) + rb;
-      const int ck = (lane % CHB) ^ wswz_xor<CHB>(row);
-      const long long p = pbase + row;
-      const void* src = g_zero16;
-      if (p < pb) {
-        if (plain) {
-          src = x + p * g.C + c0 + ck * 8;
-        } else {
-          const unsigned pu = (unsigned)p, q = pu / (unsigned)g.OW;  // M < 2^31 (host check)
-          const int ow = (int)(pu - q * (unsigned)g.OW);
-          const unsigned n = q / (unsigned)g.OH;
-          const int oh = (int)(q - n * (unsigned)g.OH);
-          const int ih = oh * g.stride + fr_ - g.pad, iw = ow * g.stride + fs_ - g.pad;
-          if ((unsigned)ih < (unsigned)g.H && (unsigned)iw < (unsigned)g.W)
-            src = x + (((long long)n * g.H + ih) * g.W + iw) * g.C + c0 + ck * 8;
-        }
-      }
-      glds16(src, B + (i * NW + wave) * (64 / CHB) * BN);
-    }
-  };
-  const int grp = lane >> 4, gi = lane & 15, q = gi >> 2, pq = gi & 3;
-  auto trfrag = [&](const T* base, int kk, int cb, auto chtag) -> frag {
-    constexpr int CH = decltype(chtag)::value;
-    const int row = 32 * kk + 8 * grp + q, col = cb + 4 * pq;
-    const T* a0 = base + wswz<CH>(row, col >> 3) + (col & 7);
-    const T* a1 = base + wswz<CH>(row + 4, col >> 3) + (col & 7);
-    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)a0);
-    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)a1);
-    typedef __attribute__((ext_vector_type(8))) short v8s;
-    const v8s v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(frag, v);
-  };
-  f32x4 acc[MT][NT];
-#pragma unroll
-  for (int a = 0; a < MT; ++a)
-#pragma unroll
-    for (int b = 0; b < NT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (steps > 0) issue(0, 0);
-  for (int t = 0; t < steps; ++t) {
-    const int buf = t & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t + 1 < steps) issue(t + 1, buf ^ 1);
-    const T* A = lds + buf * STAGE;
-    const T* B = A + BP * BM;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      frag fa[MT], fb[NT];
-#pragma unroll
-      for (int a = 0; a < MT; ++a)
-        fa[a] = trfrag(A, kk, wm * (BM / NWM) + a * 16, std::integral_constant<int, CHA>{});
-#pragma unroll
-      for (int b = 0; b < NT; ++b)
-        fb[b] = trfrag(B, kk, wn * (BN / NWN) + b * 16, std::integral_constant<int, CHB>{});
-#pragma unroll
-      for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int b = 0; b < NT; ++b) acc[a][b] = MM<T>::mma(fa[a], fb[b], acc[a][b]);
-    }
-  }
-  float* out = slab + (long long)sp * g.K * RSC;
-#pragma unroll
-  for (int a = 0; a < MT; ++a)
-#pragma unroll
-    for (int b = 0; b < NT; ++b)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int m = k0 + wm * (BM / NWM) + a * 16 + 4 * grp + j, n = n0 + wn * (BN / NWN) + b * 16 + gi;
-        if constexpr (FIX) st_wt(out + (long long)m * RSC + n, acc[a][b][j]);
-        else out[(long long)m * RSC + n] = acc[a][b][j];
-      }
-  if constexpr (FIX) {
-    __shared__ int s_flag;
-    // (last_arriver: this wave's write-through stores drained, one ticket per workgroup)
-    if (!last_arriver(tickets + tile, (unsigned)splits, &s_flag)) return;
-    // the tile's splits in split order, 8 loads in flight per lane; consecutive lanes take
-    // consecutive columns (channels of one tap: unit-stride OIHW writes on a 1x1 conv)
-    const long long plane = (long long)g.K * RSC;
-    const int st = g.R * g.S;
-    for (int e = tid; e < BM * BN; e += 64 * NW) {
-      const int r = e / BN, cn = e - r * BN;
-      const long long off = (long long)(k0 + r) * RSC + n0 + cn;
-      float t = 0.f;
-      int s0 = 0;
-      for (; s0 + 8 <= splits; s0 += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = ld_wt(slab + (s0 + u) * plane + off);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t += v[u];
-      }
-      for (; s0 < splits; ++s0) t += ld_wt(slab + s0 * plane + off);
-      const int n = n0 + cn, c = n % g.C, rs = n / g.C;  // (r*S + s)*C + c
-      grad[((long long)(k0 + r) * g.C + c) * st + rs] = t;
-    }
-  }
-}
-
-constexpr int WR_QC = 16;  // float4 columns per wgrad_reduce_kernel workgroup
-
-// grad[k][c][r][s] (fp32 OIHW) = sum over splits of slab[sp][k][(r*S + s)*C + c]:
-// a workgroup owns 64 consecutive slab columns as 16 float4 quads x 16 split groups
-// (every 4th split, fixed order, 4 loads in flight), combined through LDS in group
-// order, written in the OIHW order of a [K][Cd][Rd][Sd] gradient (Cd <= C, Rd <= R,
-// Sd <= S: the stem's padded columns are dropped here).
-__global__ void __launch_bounds__(256)
-wgrad_reduce_kernel(const float* __restrict__ slab, float* __restrict__ grad, int splits, int K, int C, int R, int S,
-                    int Cd, int Rd, int Sd) {
-  // 16 float4 columns x 16 split groups per workgroup (was 64 x 4: a grid of ~150
-  // workgroups whose lanes each waited ~6 dependent rounds of 4 loads)
-  constexpr int QC = WR_QC, SG = 256 / WR_QC;
-  __shared__ f32x4 part[SG][QC];
-  const long long RSC = (long long)R * S * C, total = (long long)K * RSC;
-  const int qd = threadIdx.x % QC, rg = threadIdx.x / QC;
-  const long long col = (blockIdx.x * (long long)QC + qd) * 4;  // total % 4 == 0 (C % 64 == 0)
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (col < total) {
-    int sp = rg;
-    for (; sp + 3 * SG < splits; sp += 4 * SG) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(slab + (long long)sp * total + col);
-      const f32x4 b = *reinterpret_cast<const f32x4*>(slab + (long long)(sp + SG) * total + col);
-      const f32x4 c = *reinterpret_cast<const f32x4*>(slab + (long long)(sp + 2 * SG) * total + col);
-      const f32x4 d = *reinterpret_cast<const f32x4*>(slab + (long long)(sp + 3 * SG) * total + col);
-      acc += a;
-      acc += b;
-      acc += c;
-      acc += d;
-    }
-    for (; sp < splits; sp += SG) acc += *reinterpret_cast<const f32x4*>(slab + (long long)sp * total + col);
-  }
-  part[rg][qd] = acc;
-  __syncthreads();
-  if (rg == 0 && col < total) {
-    f32x4 t = part[0][qd];
-#pragma unroll
-    for (int gg = 1; gg < SG; ++gg) t += part[gg][qd];
-    const int k = (int)(col / RSC);
-    const long long n = col - (long long)k * RSC;  // (r*S + s)*C + c, c % 4 == 0
-    const int c = (int)(n % C), rs = (int)(n / C), r = rs / S, s = rs - r * S;
-    if (r < Rd && s < Sd) {
-      float* o = grad + (((long long)k * Cd + c) * Rd + r) * Sd + s;
-      const int st = Rd * Sd;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (c + j < Cd) o[j * st] = t[j];
-    }
-  }
-}
-
-// The same reduction for a whole backward pass's weight gradients in ONE launch
-// (ops/conv_igemm.WgradBatch): every conv left its split partials in a slab of its own, and
-// at the end of the backward one grid covers all of them -- instead of one small, tail-bound
-// launch per conv (53 launches, ~9 us each on ResNet-50: profiles/r5a_rn_steady.txt).  The
-// entries ride in the kernel arguments by value (graph-capturable, no table upload); a
-// workgroup finds its entry by its block index (prefix blk0).  Same per-block association
-// as wgrad_reduce_kernel: bitwise the same gradients.
-constexpr int WB_MAX = 48;
-struct WBEntry {
-  const float* slab;
-  float* grad;
-  int splits, K, C, R, S, Cd, Rd, Sd;
-  long long blk0;  // first block of this entry
-};
-struct WBList {
-  int n;
-  WBEntry e[WB_MAX];
-};
-
-__global__ void __launch_bounds__(256) wgrad_reduce_batch_kernel(WBList L) {
-  constexpr int QC = WR_QC, SG = 256 / WR_QC;
-  __shared__ f32x4 part[SG][QC];
-  const long long b = blockIdx.x;
-  int lo = 0, hi = L.n - 1;  // the entry holding block b
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (L.e[mid].blk0 <= b) lo = mid; else hi = mid - 1;
-  }
-  const WBEntry& E = L.e[lo];
-  const float* __restrict__ slab = E.slab;
-  const int splits = E.splits, C = E.C, S = E.S, Cd = E.Cd, Rd = E.Rd, Sd = E.Sd;
-  const long long RSC = (long long)E.R * S * C, total = (long long)E.K * RSC;
-  const int qd = threadIdx.x % QC, rg = threadIdx.x / QC;
-  const long long col = ((b - E.blk0) * QC + qd) * 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (col < total) {
-    int sp = rg;
-    for (; sp + 3 * SG < splits; sp += 4 * SG) {
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(slab + (long long)sp * total + col);
-      const f32x4 v1 = *reinterpret_cast<const f32x4*>(slab + (long long)(sp + SG) * total + col);
-      const f32x4 v2 = *reinterpret_cast<const f32x4*>(slab + (long long)(sp + 2 * SG) * total + col);
-      const f32x4 v3 = *reinterpret_cast<const f32x4*>(slab + (long long)(sp + 3 * SG) * total + col);
-      acc += v0;
-      acc += v1;
-      acc += v2;
-      acc += v3;
-    }
-    for (; sp < splits; sp += SG) acc += *reinterpret_cast<const f32x4*>(slab + (long long)sp * total + col);
-  }
-  part[rg][qd] = acc;
-  __syncthreads();
-  if (rg == 0 && col < total) {
-    f32x4 t = part[0][qd];
-#pragma unroll
-    for (int gg = 1; gg < SG; ++gg) t += part[gg][qd];
-    const int k = (int)(col / RSC);
-    const long long n = col - (long long)k * RSC;
-    const int c = (int)(n % C), rs = (int)(n / C), r = rs / S, s_ = rs - r * S;
-    if (r < Rd && s_ < Sd) {
-      float* o = E.grad + (((long long)k * Cd + c) * Rd + r) * Sd + s_;
-      const int st = Rd * Sd;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (c + j < Cd) o[j * st] = t[j];
-    }
-  }
+  write_stats<BN>(sa, K, bn, tot, tid == 0 ? cnt[0] : 0.f);  // (lane 0 wrote, and writes, the count)
 }
 
 // ---------------------------------------------------------------------------
@@ -1559,91 +1001,33 @@ void pack_weights(at::Tensor table, int64_t n, int64_t tiles, int64_t dtype_code
   DPA_CHECK_LAUNCH();
 }
 
-static Geom geom(const at::Tensor& x, const at::Tensor& w, int stride, int pad) {
-  // x: [N, C, H, W] channels_last; w: [K, C, R, S] channels_last (= [K][R][S][C] in memory)
-  Geom g;
-  g.N = (int)x.size(0); g.C = (int)x.size(1); g.H = (int)x.size(2); g.W = (int)x.size(3);
-  g.K = (int)w.size(0); g.R = (int)w.size(2); g.S = (int)w.size(3);
-  g.stride = stride; g.pad = pad;
-  g.OH = (g.H + 2 * pad - g.R) / stride + 1;
-  g.OW = (g.W + 2 * pad - g.S) / stride + 1;
-  g.M = (long long)g.N * g.OH * g.OW;
-  return g;
-}
-
-bool supported(int64_t C, int64_t K) { return C % BK == 0 && K % 64 == 0; }
-
 static int tile_n(int64_t K) { return K % 128 == 0 ? 128 : 64; }
 
-// 1x1 convs on conv_glds_kernel (DPA_G1X1=0: the general kernel, A/B runs; g1x1_config
-// switches both at run time for tests and sweeps)
-static int g_g1x1_on = -1, g_g1x1_bp = -1;
-static long long g_g1x1_min256 = -1;
+// 1x1 convs on conv_glds_kernel (DPA_G1X1=0: the general kernel, A/B runs); its pixel tile
+// forced to 128 | 256 (DPA_G1X1_BP), or 256 from DPA_G1X1_MIN256 workgroups up (256-pixel
+// tiles measured slower: off); g1x1_config switches all three at run time for tests and sweeps
+static Knob k_g1x1_on{"DPA_G1X1", 1, knob_onoff, true}, k_g1x1_bp{"DPA_G1X1_BP", 0, knob_nonneg},
+    k_g1x1_min256{"DPA_G1X1_MIN256", 1LL << 40, knob_nonneg};
+// (on, bp, min256) -> previous; a negative argument leaves that setting alone
+std::vector<int64_t> g1x1_config(int64_t on, int64_t bp, int64_t min256) {
+  return {k_g1x1_on.set(on), k_g1x1_bp.set(bp), k_g1x1_min256.set(min256)};
+}
+static bool g1x1_enabled() { return k_g1x1_on.get() != 0; }
 
-static void g1x1_init() {
-  if (g_g1x1_on >= 0) return;
-  const char* e = std::getenv("DPA_G1X1");
-  g_g1x1_on = (e == nullptr || e[0] != '0') ? 1 : 0;
-  const char* b = std::getenv("DPA_G1X1_BP");
-  g_g1x1_bp = b != nullptr ? std::atoi(b) : 0;
-  const char* m = std::getenv("DPA_G1X1_MIN256");
-  g_g1x1_min256 = m != nullptr ? std::atoll(m) : (1LL << 40);  // 256-pixel tiles measured slower: off
-}
-
-static bool g1x1_enabled() {
-  g1x1_init();
-  return g_g1x1_on != 0;
-}
-
-// LDS buffers of conv_glds_kernel (forward / plain data gradients): 2 (default) or 3
-// (DPA_GLDS_STAGES=3; glds_config(stages) at run time)
-static int g_glds_stages = -1;
-static int glds_stages() {
-  if (g_glds_stages < 0) {
-    const char* e = std::getenv("DPA_GLDS_STAGES");
-    g_glds_stages = e != nullptr && (std::atoi(e) == 3 || std::atoi(e) == 4) ? std::atoi(e) : 2;
-  }
-  return g_glds_stages;
-}
-int64_t glds_config(int64_t stages) {
-  glds_stages();
-  const int64_t prev = g_glds_stages;
-  if (stages >= 2 && stages <= 4) g_glds_stages = (int)stages;
-  return prev;
-}
+// LDS buffers of conv_glds_kernel (forward / plain data gradients): 2 (default), 3 or 4
+// (DPA_GLDS_STAGES; glds_config(stages) at run time)
+static Knob k_glds_stages{"DPA_GLDS_STAGES", 2, [](long long v, long long keep) { return v >= 2 && v <= 4 ? v : keep; }};
+int64_t glds_config(int64_t stages) { return k_glds_stages.set(stages); }
 
 // 128-channel tiles of conv_glds_kernel narrowed to 64 when the grid would have fewer than
 // this many workgroups (DPA_G1X1_BN64_BELOW; 0 = never; bn64_config at run time)
-static long long g_bn64_below = -1;
-static long long bn64_below() {
-  if (g_bn64_below < 0) {
-    const char* e = std::getenv("DPA_G1X1_BN64_BELOW");
-    g_bn64_below = e != nullptr ? std::atoll(e) : 0LL;
-  }
-  return g_bn64_below;
-}
-int64_t bn64_config(int64_t below) {
-  bn64_below();
-  const int64_t prev = g_bn64_below;
-  if (below >= 0) g_bn64_below = below;
-  return prev;
-}
+static Knob k_bn64_below{"DPA_G1X1_BN64_BELOW", 0, knob_nonneg};
+int64_t bn64_config(int64_t below) { return k_bn64_below.set(below); }
 
 // KxK convs (any stride / padding) on the glds kernel too (DPA_G3X3=0: 1x1 only, A/B runs)
-static int g_g3x3_on = -1;
-static bool g3x3_enabled() {
-  if (g_g3x3_on < 0) {
-    const char* e = std::getenv("DPA_G3X3");
-    g_g3x3_on = (e == nullptr || e[0] != '0') ? 1 : 0;
-  }
-  return g_g3x3_on != 0;
-}
-int64_t g3x3_config(int64_t on) {
-  g3x3_enabled();
-  const int64_t prev = g_g3x3_on;
-  if (on >= 0) g_g3x3_on = on ? 1 : 0;
-  return prev;
-}
+static Knob k_g3x3_on{"DPA_G3X3", 1, knob_onoff, true};
+int64_t g3x3_config(int64_t on) { return k_g3x3_on.set(on); }
+static bool g3x3_enabled() { return k_g3x3_on.get() != 0; }
 
 // Measured and not kept (profiles/r5j_wide_ns_ab.txt): the 8-wave 128 x 128 tile with three or
 // four LDS stages (two / three tiles in flight, one workgroup per CU) -- no faster even where
@@ -1654,20 +1038,8 @@ int64_t g3x3_config(int64_t on) {
 // (DPA_WIDE; wide_config at run time): 0 off, 1 auto (see wide_pick), 2 force 256 x 128,
 // 3 force 256 x 256, 4 force 128 x 128 on 8 waves.  Shapes a forced tile does not fit keep
 // the 4-wave kernel.
-static int g_wide = -1;
-static int wide_mode() {
-  if (g_wide < 0) {
-    const char* e = std::getenv("DPA_WIDE");
-    g_wide = e != nullptr ? std::atoi(e) : 1;
-  }
-  return g_wide;
-}
-int64_t wide_config(int64_t m) {
-  wide_mode();
-  const int64_t prev = g_wide;
-  if (m >= 0) g_wide = (int)m;
-  return prev;
-}
+static Knob k_wide{"DPA_WIDE", 1, knob_nonneg};
+int64_t wide_config(int64_t m) { return k_wide.set(m); }
 // -> 0 (the 4-wave 128 x 128 / x 64 tiles), 1 (256 x 128), 2 (256 x 256), 3 (128 x 128, 8 waves).
 // Auto (profiles/r5c_wide_ab.txt, every ResNet-50 forward shape): 8 waves on the 128 x 128
 // tile wherever Cout % 128 == 0 (the second wave on each SIMD hides the other's fragment-read
@@ -1675,7 +1047,7 @@ int64_t wide_config(int64_t m) {
 // (C R S >= 1024) and the grid still fills the chip (>= 196 workgroups: 40.5 vs 42.9-44.3 us
 // on 1024 -> 512 at 14x14).  bs: BN backward sums in the epilogue (128-pixel tiles only).
 static int wide_pick(long long M, int64_t K, int64_t CRS, bool bs) {
-  const int m = wide_mode();
+  const long long m = k_wide.get();
   const long long r256 = (M + 255) / 256;
   const bool ok2 = !bs && K % 256 == 0 && r256 <= S1_MAXROWS;  // the deferred tree: one level at BN = 256
   const bool ok1 = K % 128 == 0;
@@ -1691,63 +1063,51 @@ static int wide_pick(long long M, int64_t K, int64_t CRS, bool bs) {
 // 2 per CU: the 96 KB of LDS leave one 256-pixel workgroup per CU), else 128 (64 KB: two
 // per CU); DPA_G1X1_BP=128|256 forces one.
 static int g1x1_bp(long long M, int64_t K) {
-  g1x1_init();
-  if (g_g1x1_bp == 128 || g_g1x1_bp == 256) return g_g1x1_bp;
+  const long long bp = k_g1x1_bp.get();
+  if (bp == 128 || bp == 256) return (int)bp;
   const long long t256 = (M + 255) / 256 * (K / tile_n(K));
-  return t256 >= g_g1x1_min256 ? 256 : 128;
+  return t256 >= k_g1x1_min256.get() ? 256 : 128;
 }
 
 // deferred statistics tree (StatArgs.defer + stat_tree_kernel) for grids of more than
-// g_defer_min workgroups (several rounds per CU: the in-launch hand-off is then paid
-// serially by every round); DPA_STAT_DEFER_MIN overrides, 0 = always, -1 = never
-static long long g_defer_min = -2;
-static bool defer_stats(long long blocks) {
-  if (g_defer_min == -2) {
-    const char* e = std::getenv("DPA_STAT_DEFER_MIN");
-    g_defer_min = e != nullptr ? std::atoll(e) : 0LL;  // always: measured 14.73 vs 14.77-14.84 ms (1024)
-  }
-  return g_defer_min >= 0 && blocks > g_defer_min;
-}
-int64_t stat_defer_config(int64_t min_blocks) {
-  defer_stats(0);
-  const int64_t prev = g_defer_min;
-  if (min_blocks >= -1) g_defer_min = min_blocks;
-  return prev;
-}
+// DPA_STAT_DEFER_MIN workgroups (several rounds per CU: the in-launch hand-off is then paid
+// serially by every round); 0 = always (the default: measured 14.73 vs 14.77-14.84 ms at
+// 1024), -1 = never; stat_defer_config at run time (-2 leaves it alone)
+static Knob k_defer_min{"DPA_STAT_DEFER_MIN", 0, [](long long v, long long keep) { return v >= -1 ? v : keep; }};
+int64_t stat_defer_config(int64_t min_blocks) { return k_defer_min.set(min_blocks); }
+static bool defer_stats(long long blocks) { return k_defer_min.get() >= 0 && blocks > k_defer_min.get(); }
+
+// The instantiated variants: stat_sum1_kernel <BN, NL>, stat_tree_kernel <BN>
+using Sum1Variants = std::tuple<Var<256, 16>, Var<128, 16>, Var<64, 16>, Var<256, S1_MAXROWS / S1_RG>,
+                                Var<128, S1_MAXROWS / S1_RG>, Var<64, S1_MAXROWS / S1_RG>>;
+using TreeVariants = std::tuple<Var<128>, Var<64>>;
 
 static void launch_stat_tree(StatArgs sa, long long M, int bm, int K, int BN) {
   const long long rows = (M + bm - 1) / bm, NG = (rows + G1 - 1) / G1;
-  if (rows <= S1_MAXROWS) {  // one level: every row in flight at once, no ticket
-    const dim3 gr((unsigned)(K / BN), (unsigned)(2 * BN / S1_COLS)), th(S1_THR);
+  bool found;
+  if (rows <= S1_MAXROWS) {  // one level: every row in flight at once (16 or 64 per lane), no ticket
+    const dim3 gr((unsigned)(K / BN), (unsigned)(2 * BN / S1_COLS));
     xgmi::set_site_grid(sa.xs, (long long)gr.x * gr.y, "stat_sum1");  // SyncBN finishers: every workgroup
-    if (rows <= 16 * S1_RG) {
-      if (BN == 256) hipLaunchKernelGGL((stat_sum1_kernel<256, 16>), gr, th, 0, cur_stream(), sa, M, bm, K);
-      else if (BN == 128) hipLaunchKernelGGL((stat_sum1_kernel<128, 16>), gr, th, 0, cur_stream(), sa, M, bm, K);
-      else hipLaunchKernelGGL((stat_sum1_kernel<64, 16>), gr, th, 0, cur_stream(), sa, M, bm, K);
-    } else {
-      if (BN == 256) hipLaunchKernelGGL((stat_sum1_kernel<256, S1_MAXROWS / S1_RG>), gr, th, 0, cur_stream(), sa, M, bm, K);
-      else if (BN == 128) hipLaunchKernelGGL((stat_sum1_kernel<128, S1_MAXROWS / S1_RG>), gr, th, 0, cur_stream(), sa, M, bm, K);
-      else hipLaunchKernelGGL((stat_sum1_kernel<64, S1_MAXROWS / S1_RG>), gr, th, 0, cur_stream(), sa, M, bm, K);
-    }
-    DPA_CHECK_LAUNCH();
-    return;
+    const int NL = rows <= 16 * S1_RG ? 16 : S1_MAXROWS / S1_RG;
+    found = for_variant(Sum1Variants{}, [&](auto v) {
+      using V = decltype(v);
+      if (!V::is({BN, NL})) return false;
+      hipLaunchKernelGGL((stat_sum1_kernel<V::v[0], V::v[1]>), gr, dim3(S1_THR), 0, cur_stream(), sa, M, bm, K);
+      return true;
+    });
+  } else {
+    TORCH_CHECK(BN <= 128, "stat_tree: 256-channel tiles need <= ", S1_MAXROWS, " pixel tiles");
+    xgmi::set_site_grid(sa.xs, K / BN, "stat_tree");  // SyncBN finishers: the last arriver of each channel tile
+    found = for_variant(TreeVariants{}, [&](auto v) {
+      using V = decltype(v);
+      if (!V::is({BN})) return false;
+      hipLaunchKernelGGL(stat_tree_kernel<V::v[0]>, dim3((unsigned)(NG * (K / BN))), dim3(THR), 0, cur_stream(), sa, M,
+                         bm, K);
+      return true;
+    });
   }
-  TORCH_CHECK(BN <= 128, "stat_tree: 256-channel tiles need <= ", S1_MAXROWS, " pixel tiles");
-  const dim3 gr((unsigned)(NG * (K / BN))), th(THR);
-  xgmi::set_site_grid(sa.xs, K / BN, "stat_tree");  // SyncBN finishers: the last arriver of each channel tile
-  if (BN == 128) hipLaunchKernelGGL(stat_tree_kernel<128>, gr, th, 0, cur_stream(), sa, M, bm, K);
-  else hipLaunchKernelGGL(stat_tree_kernel<64>, gr, th, 0, cur_stream(), sa, M, bm, K);
+  TORCH_CHECK(found, "stat_tree: no kernel variant for ", BN, "-channel tiles");
   DPA_CHECK_LAUNCH();
-}
-
-// (on, bp, min256) -> previous; a negative argument leaves that setting alone
-std::vector<int64_t> g1x1_config(int64_t on, int64_t bp, int64_t min256) {
-  g1x1_init();
-  std::vector<int64_t> prev{g_g1x1_on, g_g1x1_bp, g_g1x1_min256};
-  if (on >= 0) g_g1x1_on = on ? 1 : 0;
-  if (bp >= 0) g_g1x1_bp = (int)bp;
-  if (min256 >= 0) g_g1x1_min256 = min256;
-  return prev;
 }
 
 // statistics workspace: level-1 + level-2 partial rows (floats) and tickets (int32)
@@ -1759,6 +1119,26 @@ int64_t stat_tickets_len(int64_t M, int64_t K) {
   const int64_t rows = (M + BM - 1) / BM, ng = (rows + G1 - 1) / G1;
   return (K / 64) * (ng + 1);  // 64-channel tiles at most (conv_glds_kernel may narrow 128 -> 64)
 }
+
+// The instantiated variants: conv_fwd_kernel <BN, MODE>, conv_glds_kernel
+// <BP, BN, BS, KXK, NS, NWP, NWC>
+using FwdVariants = std::tuple<Var<128, MODE_GEN>, Var<64, MODE_GEN>, Var<128, MODE_STEM>, Var<64, MODE_STEM>,
+                               Var<128, MODE_S2T>, Var<64, MODE_S2T>>;
+using GldsVariants = std::tuple<
+    // 4 waves, two LDS buffers: 1x1 (pixel tile 256 | 128) and KxK
+    Var<256, 128, BS_NONE, 0, 2, 2, 2>, Var<256, 64, BS_NONE, 0, 2, 2, 2>, Var<128, 128, BS_NONE, 0, 2, 2, 2>,
+    Var<128, 64, BS_NONE, 0, 2, 2, 2>, Var<128, 128, BS_NONE, 1, 2, 2, 2>, Var<128, 64, BS_NONE, 1, 2, 2, 2>,
+    // three / four LDS buffers
+    Var<128, 128, BS_NONE, 0, 3, 2, 2>, Var<128, 64, BS_NONE, 0, 3, 2, 2>, Var<128, 128, BS_NONE, 1, 3, 2, 2>,
+    Var<128, 64, BS_NONE, 1, 3, 2, 2>, Var<128, 128, BS_NONE, 0, 4, 2, 2>, Var<128, 64, BS_NONE, 0, 4, 2, 2>,
+    Var<128, 128, BS_NONE, 1, 4, 2, 2>, Var<128, 64, BS_NONE, 1, 4, 2, 2>,
+    // wide tiles, 8 waves
+    Var<256, 128, BS_NONE, 0, 2, 4, 2>, Var<256, 128, BS_NONE, 1, 2, 4, 2>, Var<256, 256, BS_NONE, 0, 2, 2, 4>,
+    Var<256, 256, BS_NONE, 1, 2, 2, 4>, Var<128, 128, BS_NONE, 0, 2, 2, 4>, Var<128, 128, BS_NONE, 1, 2, 2, 4>,
+    // BN backward sums in the epilogue: 4 waves, and 128 x 128 on 8
+    Var<128, 128, BS_Y, 0, 2, 2, 2>, Var<128, 64, BS_Y, 0, 2, 2, 2>, Var<128, 128, BS_Y, 0, 2, 2, 4>,
+    Var<128, 128, BS_REC, 0, 2, 2, 2>, Var<128, 64, BS_REC, 0, 2, 2, 2>, Var<128, 128, BS_REC, 0, 2, 2, 4>,
+    Var<128, 128, BS_REC, 1, 2, 2, 2>, Var<128, 64, BS_REC, 1, 2, 2, 2>, Var<128, 128, BS_REC, 1, 2, 2, 4>>;
 
 // y: [N, K, OH, OW] channels_last (preallocated).  With `stats` (fp32 [3K+4], the
 // bn_nhwc layout), also part / tickets (stat_part_len / stat_tickets_len; tickets
@@ -1876,10 +1256,10 @@ void conv_fwd(at::Tensor x, at::Tensor w, at::Tensor y, int64_t stride, int64_t 
   if (mode == MODE_GEN && g1x1_enabled() && x.numel() < (1LL << 31) && w.numel() < (1LL << 31) &&
       (g3x3_enabled() || (g.R == 1 && g.S == 1 && g.pad == 0))) {
     // the glds-staged implicit-GEMM kernel (pixel tile 256 or 128, see g1x1_bp; 64-channel
-    // tiles when 128-channel ones leave the grid below g_bn64_below workgroups)
+    // tiles when 128-channel ones leave the grid below DPA_G1X1_BN64_BELOW workgroups)
     const int wide = wide_pick(g.M, g.K, (int64_t)g.C * g.R * g.S, bwdst);
     int BP = (bwdst || !(g.R == 1 && g.S == 1 && g.pad == 0)) ? 128 : g1x1_bp(g.M, g.K);
-    int BN = BN0 == 128 && BP == 128 && (g.M + 127) / 128 * (g.K / 128) < bn64_below() ? 64 : BN0;
+    int BN = BN0 == 128 && BP == 128 && (g.M + 127) / 128 * (g.K / 128) < k_bn64_below.get() ? 64 : BN0;
     if (wide == 1 || wide == 2) BP = 256;
     if (wide == 1 || wide == 3) BN = 128;
     if (wide == 2) BN = 256;
@@ -1896,12 +1276,20 @@ void conv_fwd(at::Tensor x, at::Tensor w, at::Tensor y, int64_t stride, int64_t 
       sa.bwd = 1;
       sa.defer = 1;
     }
+    // the tile configuration <BP, BN, BS, KXK, NS, NWP, NWC>.  Waves: the wide tiles run 8
+    // (256 x 128 as 4 x 2, the others 2 x 4).  BS_Y stays on 4 waves unless forced
+    // (DPA_WIDE=4): its epilogue prefetches three operand rows, and 8 waves measured +218 us
+    // over the network's 12 launches (profiles/r5d_resnet50_steady_wide.txt).  Three / four
+    // LDS buffers (one workgroup per CU): the 4-wave 128-pixel tiles without BN sums.
+    const bool kxk = !(g.R == 1 && g.S == 1 && g.pad == 0);  // KxK: tap-walking loader (128-pixel tiles)
+    TORCH_CHECK(!(bwdst && kxk && bn_y.has_value()), "conv_fwd: KxK BN sums take the recomputed mask");
+    const int BS = !bwdst ? BS_NONE : bn_y.has_value() ? BS_Y : BS_REC;
+    const bool w8 = wide != 0 && !(BS == BS_Y && !(wide == 3 && k_wide.get() == 4));
+    const int NWP = w8 && wide == 1 ? 4 : 2, NWC = w8 ? 8 / NWP : 2;
+    const long long stages = k_glds_stages.get();
+    const int NS = !wide && !bwdst && BP == 128 && (stages == 3 || stages == 4) ? (int)stages : 2;
     auto launch = [&](auto tag) {
       using T = decltype(tag);
-      const T* xp = reinterpret_cast<const T*>(x.data_ptr());
-      const T* wp = reinterpret_cast<const T*>(w.data_ptr());
-      T* yp = reinterpret_cast<T*>(y.data_ptr());
-      const dim3 gr((unsigned)blocks), th(THR);
       BwdStatArgs<T> bs;
       if (bwdst) {
         bs.x = reinterpret_cast<const T*>(bn_x->data_ptr());
@@ -1909,61 +1297,20 @@ void conv_fwd(at::Tensor x, at::Tensor w, at::Tensor y, int64_t stride, int64_t 
         bs.save = bn_save->data_ptr<float>();
         bs.gamma = bn_gamma.has_value() ? bn_gamma->data_ptr<float>() : nullptr;
         bs.beta = bn_beta.has_value() ? bn_beta->data_ptr<float>() : nullptr;
-        const dim3 t8(512);
-        if (!(g.R == 1 && g.S == 1 && g.pad == 0)) {  // KxK data gradient (recomputed ReLU mask)
-          TORCH_CHECK(!bn_y.has_value(), "conv_fwd: KxK BN sums take the recomputed mask");
-          if (wide == 3) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_REC, true, 2, 2, 4>), gr, t8, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-          else if (BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_REC, true>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-          else hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64, BS_REC, true>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        } else if (bn_y.has_value()) {
-          // BS_Y stays on 4 waves unless forced (DPA_WIDE=4): its epilogue prefetches three
-          // operand rows, and 8 waves measured +218 us over the network's 12 launches
-          // (profiles/r5d_resnet50_steady_wide.txt)
-          if (wide == 3 && wide_mode() == 4) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_Y, false, 2, 2, 4>), gr, t8, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-          else if (BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_Y>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-          else hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64, BS_Y>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        } else {
-          if (wide == 3) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_REC, false, 2, 2, 4>), gr, t8, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-          else if (BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_REC>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-          else hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64, BS_REC>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        }
-        return;
       }
-      const bool kxk = !(g.R == 1 && g.S == 1 && g.pad == 0);
-      if (wide) {  // 8 waves
-        if (wide == 1 && kxk) hipLaunchKernelGGL((conv_glds_kernel<T, 256, 128, BS_NONE, true, 2, 4, 2>), gr, dim3(512), 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else if (wide == 1) hipLaunchKernelGGL((conv_glds_kernel<T, 256, 128, BS_NONE, false, 2, 4, 2>), gr, dim3(512), 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else if (wide == 2 && kxk) hipLaunchKernelGGL((conv_glds_kernel<T, 256, 256, BS_NONE, true, 2, 2, 4>), gr, dim3(512), 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else if (wide == 2) hipLaunchKernelGGL((conv_glds_kernel<T, 256, 256, BS_NONE, false, 2, 2, 4>), gr, dim3(512), 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else if (kxk) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_NONE, true, 2, 2, 4>), gr, dim3(512), 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_NONE, false, 2, 2, 4>), gr, dim3(512), 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        return;
-      }
-      if (glds_stages() == 3 && BP == 128) {  // three LDS buffers (one workgroup per CU)
-        if (kxk && BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_NONE, true, 3>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else if (kxk) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64, BS_NONE, true, 3>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else if (BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_NONE, false, 3>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64, BS_NONE, false, 3>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        return;
-      }
-      if (glds_stages() == 4 && BP == 128) {  // four LDS buffers (three tiles in flight)
-        if (kxk && BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_NONE, true, 4>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else if (kxk) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64, BS_NONE, true, 4>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else if (BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_NONE, false, 4>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64, BS_NONE, false, 4>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        return;
-      }
-      if (kxk) {  // KxK: tap-walking loader (128-pixel tiles)
-        if (BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128, BS_NONE, true>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        else hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64, BS_NONE, true>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-        return;
-      }
-      if (BP == 256 && BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 256, 128>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-      else if (BP == 256) hipLaunchKernelGGL((conv_glds_kernel<T, 256, 64>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-      else if (BN == 128) hipLaunchKernelGGL((conv_glds_kernel<T, 128, 128>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
-      else hipLaunchKernelGGL((conv_glds_kernel<T, 128, 64>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g, bs);
+      return for_variant(GldsVariants{}, [&](auto v) {
+        using V = decltype(v);
+        if (!V::is({BP, BN, BS, kxk, NS, NWP, NWC})) return false;
+        hipLaunchKernelGGL((conv_glds_kernel<T, V::v[0], V::v[1], V::v[2], V::v[3] != 0, V::v[4], V::v[5], V::v[6]>),
+                           dim3((unsigned)blocks), dim3(64 * NWP * NWC), 0, cur_stream(),
+                           reinterpret_cast<const T*>(x.data_ptr()), reinterpret_cast<const T*>(w.data_ptr()),
+                           reinterpret_cast<T*>(y.data_ptr()), sa, g, bs);
+        return true;
+      });
     };
-    if (x.scalar_type() == at::kBFloat16) launch(__hip_bfloat16{}); else launch(__half{});
+    const bool found = x.scalar_type() == at::kBFloat16 ? launch(__hip_bfloat16{}) : launch(__half{});
+    TORCH_CHECK(found, "conv_fwd: no glds kernel variant for tile ", BP, " x ", BN, " (BS ", BS, ", KxK ", kxk, ", ",
+                NS, " stages, ", NWP, " x ", NWC, " waves)");
     DPA_CHECK_LAUNCH();
     if (sa.defer) launch_stat_tree(sa, g.M, BP, (int)g.K, BN);
     return;
@@ -1976,238 +1323,19 @@ void conv_fwd(at::Tensor x, at::Tensor w, at::Tensor y, int64_t stride, int64_t 
   sa.defer = st && (defer_stats(blocks) || xc) ? 1 : 0;
   auto launch = [&](auto tag) {
     using T = decltype(tag);
-    const T* xp = reinterpret_cast<const T*>(x.data_ptr());
-    const T* wp = reinterpret_cast<const T*>(w.data_ptr());
-    T* yp = reinterpret_cast<T*>(y.data_ptr());
-    const dim3 gr((unsigned)blocks), th(THR);
-    if (mode == MODE_STEM) {
-      if (BN == 128) hipLaunchKernelGGL((conv_fwd_kernel<T, 128, MODE_STEM>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g);
-      else hipLaunchKernelGGL((conv_fwd_kernel<T, 64, MODE_STEM>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g);
-    } else if (mode == MODE_S2T) {
-      if (BN == 128) hipLaunchKernelGGL((conv_fwd_kernel<T, 128, MODE_S2T>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g);
-      else hipLaunchKernelGGL((conv_fwd_kernel<T, 64, MODE_S2T>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g);
-    } else {
-      if (BN == 128) hipLaunchKernelGGL((conv_fwd_kernel<T, 128>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g);
-      else hipLaunchKernelGGL((conv_fwd_kernel<T, 64>), gr, th, 0, cur_stream(), xp, wp, yp, sa, g);
-    }
+    return for_variant(FwdVariants{}, [&](auto v) {
+      using V = decltype(v);
+      if (!V::is({BN, (int)mode})) return false;
+      hipLaunchKernelGGL((conv_fwd_kernel<T, V::v[0], V::v[1]>), dim3((unsigned)blocks), dim3(THR), 0, cur_stream(),
+                         reinterpret_cast<const T*>(x.data_ptr()), reinterpret_cast<const T*>(w.data_ptr()),
+                         reinterpret_cast<T*>(y.data_ptr()), sa, g);
+      return true;
+    });
   };
-  if (x.scalar_type() == at::kBFloat16) launch(__hip_bfloat16{}); else launch(__half{});
+  const bool found = x.scalar_type() == at::kBFloat16 ? launch(__hip_bfloat16{}) : launch(__half{});
+  TORCH_CHECK(found, "conv_fwd: no kernel variant for ", BN, "-channel tiles, mode ", mode);
   DPA_CHECK_LAUNCH();
   if (sa.defer) launch_stat_tree(sa, g.M, BM, (int)g.K, BN);
-}
-
-// weight gradients on conv_wgrad_glds_kernel: DPA_WGRAD_GLDS = 1 (default) the 1x1 convs,
-// 2 every MODE_GEN conv, 0 none (the register-staged kernel); wgrad_config sets it at run time
-static int g_wgrad_glds = -1;
-static int wgrad_glds() {
-  if (g_wgrad_glds < 0) {
-    const char* e = std::getenv("DPA_WGRAD_GLDS");
-    // 2 (every MODE_GEN conv, 3x3 included, with 8-wave workgroups): network wgrad 2600 vs
-    // 2668 us (1x1 only) vs 2760 (4 waves): profiles/r5d_wgrad_ab.txt
-    g_wgrad_glds = e == nullptr ? 2 : std::atoi(e);
-  }
-  return g_wgrad_glds;
-}
-int64_t wgrad_config(int64_t glds) {
-  wgrad_glds();
-  const int64_t prev = g_wgrad_glds;
-  if (glds >= 0) g_wgrad_glds = (int)glds;
-  return prev;
-}
-// waves per workgroup of conv_wgrad_glds_kernel: 8 (default) or 4 (DPA_WGRAD_WAVES; wgrad_waves_config)
-static int g_wgrad_waves = -1;
-static int wgrad_waves() {
-  if (g_wgrad_waves < 0) {
-    const char* e = std::getenv("DPA_WGRAD_WAVES");
-    g_wgrad_waves = e != nullptr && std::atoi(e) == 4 ? 4 : 8;  // 8: network wgrad 2668 vs 2760 us
-  }
-  return g_wgrad_waves;
-}
-int64_t wgrad_waves_config(int64_t w) {
-  wgrad_waves();
-  const int64_t prev = g_wgrad_waves;
-  if (w == 4 || w == 8) g_wgrad_waves = (int)w;
-  return prev;
-}
-
-// wgrad tile shapes: BM | Cout, BN | C (a column tile stays inside one filter tap)
-static int wtile(int64_t v) { return v % 128 == 0 ? 128 : 64; }
-
-// In-launch split-K reduction (conv_wgrad_glds_kernel FIX) for convs of at most
-// DPA_WGRAD_FIXUP_MAXSP splits (default 0: off; wgrad_fixup_config sets it).  Measured
-// slower on ResNet-50 at every bound -- 13.77 ms off, 14.02 at 8 splits, 14.74 at 32, 17.69
-// for every conv (profiles/r6v_wgrad_fixup_ab.txt): the partial tiles' write-through stores
-// and each tile's serial last-arriver sum cost more than the separate, fully parallel launch.  Tickets: one
-// zeroed device array per device, re-armed by every tile's last arriver; allocated outside
-// any capture (a first use inside one takes the reduce launch instead).
-static long long g_fix_maxsp = -1;
-static long long fix_maxsp() {
-  if (g_fix_maxsp < 0) {
-    const char* e = std::getenv("DPA_WGRAD_FIXUP_MAXSP");
-    g_fix_maxsp = e != nullptr ? std::atoll(e) : 0LL;
-  }
-  return g_fix_maxsp;
-}
-int64_t wgrad_fixup_config(int64_t maxsp) {
-  const int64_t prev = fix_maxsp();
-  if (maxsp >= 0) g_fix_maxsp = maxsp;
-  return prev;
-}
-constexpr int kFixTickets = 4096;
-static unsigned* fix_tickets(long long tiles) {
-  static unsigned* per_dev[64] = {};
-  if (tiles > kFixTickets) return nullptr;
-  int dev = 0;
-  DPA_CHECK_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return nullptr;
-  if (per_dev[dev] == nullptr) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    DPA_CHECK_HIP(hipStreamIsCapturing(cur_stream(), &st));
-    if (st != hipStreamCaptureStatusNone) return nullptr;
-    unsigned* p = nullptr;
-    DPA_CHECK_HIP(hipMalloc(&p, kFixTickets * sizeof(unsigned)));
-    DPA_CHECK_HIP(hipMemset(p, 0, kFixTickets * sizeof(unsigned)));
-    DPA_CHECK_HIP(hipDeviceSynchronize());
-    per_dev[dev] = p;
-  }
-  return per_dev[dev];
-}
-
-int64_t wgrad_splits(int64_t M, int64_t K, int64_t C, int64_t R, int64_t S) {
-  // ~2 workgroups per CU, each at least 16 K-steps of 64 pixels, and the fp32
-  // partials at most ~48 MB (written and re-read once: ~12 us at HBM rate)
-  const int64_t tiles = (K / wtile(K)) * (R * S * C / wtile(C));
-  static const int64_t target = [] {
-    const char* e = std::getenv("DPA_WGRAD_BLOCKS");
-    return e != nullptr ? std::atoll(e) : 512LL;  // ResNet-50 sweep: 384 15.01, 512 14.50, 768 14.59, 1024 14.67 ms
-  }();
-  static const int64_t minpix = [] {  // round 6 re-sweep: 1024 13.81, 512 13.73, 384 13.74, 256 13.72 ms
-    const char* e = std::getenv("DPA_WGRAD_MINPIX");    // (profiles/r6bb_rn_wgrad_minpix.txt)
-    return e != nullptr ? std::atoll(e) : 512LL;
-  }();
-  int64_t sp = std::max<int64_t>(1, target / tiles);
-  sp = std::min<int64_t>(sp, std::max<int64_t>(1, M / minpix));
-  sp = std::min<int64_t>(sp, std::max<int64_t>(1, (12LL << 20) / (K * R * S * C)));
-  return sp;
-}
-
-// dy: [N, K, OH, OW] channels_last; x: [N, C, H, W] channels_last; grad: fp32 [K, C, R, S]
-// contiguous (written, not accumulated); slab: fp32 >= splits * K * R*S*C.
-// mode MODE_STEM: x = the stem_pack image [N, 4, H, W], grad [K, 3, 7, 7] (stride 2, pad 3).
-std::vector<int64_t> conv_wgrad(at::Tensor dy, at::Tensor x, at::Tensor grad, int64_t stride, int64_t pad,
-                                at::Tensor slab, int64_t mode, bool reduce) {
-  TORCH_CHECK(dy.is_cuda() && x.is_cuda() && grad.is_cuda() && slab.is_cuda(), "conv_wgrad: device tensors");
-  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf),
-              "conv_wgrad: bf16 / f16 activations");
-  TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) && x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_wgrad: channels_last dy / x");
-  TORCH_CHECK(grad.scalar_type() == at::kFloat && grad.is_contiguous() && grad.dim() == 4, "conv_wgrad: fp32 grad");
-  const bool stem = mode == MODE_STEM;
-  TORCH_CHECK(mode == MODE_GEN || stem, "conv_wgrad: mode");
-  Geom g = geom(x, grad, (int)stride, (int)pad);
-  int Cd = g.C, Rd = g.R, Sd = g.S;  // gradient dims (the stem's padded K space drops to these)
-  if (stem) {
-    TORCH_CHECK(x.size(1) == 4 && grad.size(1) == 3 && g.R == 7 && g.S == 7 && stride == 2 && pad == 3 &&
-                    g.K % 64 == 0, "conv_wgrad: stem needs the stem_pack image and a [K, 3, 7, 7] gradient");
-    g.C = 4;
-    Cd = 3;
-  } else {
-    TORCH_CHECK(grad.size(1) == g.C && supported(g.C, g.K), "conv_wgrad: needs C % 64 == 0 and Cout % 64 == 0");
-  }
-  TORCH_CHECK(dy.size(0) == g.N && dy.size(1) == g.K && dy.size(2) == g.OH && dy.size(3) == g.OW, "conv_wgrad: dy");
-  TORCH_CHECK(g.M < (1LL << 31), "conv_wgrad: too many pixels");
-  const int SR = stem ? 8 : g.R, SS = stem ? 8 : g.S;  // slab column space [SR][SS][C]
-  const int64_t sp = wgrad_splits(g.M, g.K, g.C, SR, SS);
-  const int64_t RSC = (int64_t)SR * SS * g.C;
-  TORCH_CHECK(slab.scalar_type() == at::kFloat && slab.numel() >= sp * g.K * RSC, "conv_wgrad: slab too small");
-  const long long pps = ((g.M + sp - 1) / sp + 63) / 64 * 64;
-  const int BM = wtile(g.K), BN = wtile(g.C);
-  const long long blocks = sp * (g.K / BM) * (RSC / BN);
-  // in-launch split-K reduction: 8-wave LDS-DMA kernels, reduced gradients wanted
-  const bool glds = !stem && ((g.R == 1 && g.S == 1 && wgrad_glds() >= 1) || wgrad_glds() == 2);
-  unsigned* tk = nullptr;
-  const bool fixed = reduce && glds && wgrad_waves() == 8 && sp <= fix_maxsp() &&
-                     (tk = fix_tickets((g.K / BM) * (RSC / BN))) != nullptr;
-  auto launch = [&](auto tag) {
-    using T = decltype(tag);
-    const T* dp = reinterpret_cast<const T*>(dy.data_ptr());
-    const T* xp = reinterpret_cast<const T*>(x.data_ptr());
-    float* sl = slab.data_ptr<float>();
-    const dim3 gr((unsigned)blocks), th(THR);
-    // 1x1 (mode 1, default) or every MODE_GEN conv (mode 2): on 3x3 it measured ~5 % slower
-    if (!stem && ((g.R == 1 && g.S == 1 && wgrad_glds() >= 1) || wgrad_glds() == 2)) {
-      float* gp = grad.data_ptr<float>();
-      if (wgrad_waves() == 8) {
-        const dim3 t8(512);
-        if (fixed) {
-          if (BM == 128 && BN == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 128, 128, 2, 4, true>), gr, t8, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, tk);
-          else if (BM == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 128, 64, 4, 2, true>), gr, t8, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, tk);
-          else if (BN == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 64, 128, 2, 4, true>), gr, t8, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, tk);
-          else hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 64, 64, 2, 4, true>), gr, t8, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, tk);
-          return;
-        }
-        if (BM == 128 && BN == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 128, 128, 2, 4>), gr, t8, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, nullptr);
-        else if (BM == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 128, 64, 4, 2>), gr, t8, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, nullptr);
-        else if (BN == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 64, 128, 2, 4>), gr, t8, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, nullptr);
-        else hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 64, 64, 2, 4>), gr, t8, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, nullptr);
-        return;
-      }
-      if (BM == 128 && BN == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 128, 128>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, nullptr);
-      else if (BM == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 128, 64>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, nullptr);
-      else if (BN == 128) hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 64, 128>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, nullptr);
-      else hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, 64, 64>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, gp, nullptr);
-      return;
-    }
-    if (stem && BM == 128) hipLaunchKernelGGL((conv_wgrad_kernel<T, 128, 64, MODE_STEM>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps);
-    else if (stem) hipLaunchKernelGGL((conv_wgrad_kernel<T, 64, 64, MODE_STEM>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps);
-    else if (BM == 128 && BN == 128) hipLaunchKernelGGL((conv_wgrad_kernel<T, 128, 128>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps);
-    else if (BM == 128) hipLaunchKernelGGL((conv_wgrad_kernel<T, 128, 64>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps);
-    else if (BN == 128) hipLaunchKernelGGL((conv_wgrad_kernel<T, 64, 128>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<T, 64, 64>), gr, th, 0, cur_stream(), dp, xp, sl, g, (int)sp, pps);
-  };
-  if (x.scalar_type() == at::kBFloat16) launch(__hip_bfloat16{}); else launch(__half{});
-  DPA_CHECK_LAUNCH();
-  // reduce = false: the slab stays for wgrad_reduce_batch (the geometry below is its entry)
-  std::vector<int64_t> geo{sp, g.K, g.C, SR, SS, Cd, Rd, Sd};
-  if (!reduce || fixed) return geo;
-  const long long total = (long long)g.K * RSC;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 4 * WR_QC - 1) / (4 * WR_QC))), dim3(256), 0,
-                     cur_stream(),
-                     slab.data_ptr<float>(), grad.data_ptr<float>(), (int)sp, g.K, g.C, SR, SS, Cd, Rd, Sd);
-  DPA_CHECK_LAUNCH();
-  return geo;
-}
-
-// One launch reducing every (slab, grad) pair of a backward pass (conv_wgrad with reduce =
-// false; geo = the geometry it returned), WB_MAX entries per launch.
-void wgrad_reduce_batch(std::vector<at::Tensor> slabs, std::vector<at::Tensor> grads,
-                        std::vector<std::vector<int64_t>> geos) {
-  TORCH_CHECK(slabs.size() == grads.size() && slabs.size() == geos.size(), "wgrad_reduce_batch: one geometry per pair");
-  for (size_t s0 = 0; s0 < slabs.size(); s0 += WB_MAX) {
-    WBList L{};
-    long long blk = 0;
-    const size_t e = std::min(slabs.size(), s0 + (size_t)WB_MAX);
-    for (size_t i = s0; i < e; ++i) {
-      const auto& q = geos[i];
-      TORCH_CHECK(q.size() == 8, "wgrad_reduce_batch: geometry {splits, K, C, R, S, Cd, Rd, Sd}");
-      const long long total = q[1] * q[3] * q[4] * q[2];
-      TORCH_CHECK(slabs[i].is_cuda() && slabs[i].scalar_type() == at::kFloat && slabs[i].numel() >= q[0] * total,
-                  "wgrad_reduce_batch: slab");
-      TORCH_CHECK(grads[i].is_cuda() && grads[i].scalar_type() == at::kFloat && grads[i].is_contiguous() &&
-                      grads[i].numel() == q[1] * q[5] * q[6] * q[7], "wgrad_reduce_batch: fp32 OIHW grad");
-      WBEntry& E = L.e[i - s0];
-      E.slab = slabs[i].data_ptr<float>();
-      E.grad = grads[i].data_ptr<float>();
-      E.splits = (int)q[0]; E.K = (int)q[1]; E.C = (int)q[2]; E.R = (int)q[3]; E.S = (int)q[4];
-      E.Cd = (int)q[5]; E.Rd = (int)q[6]; E.Sd = (int)q[7];
-      E.blk0 = blk;
-      blk += (total + 4 * WR_QC - 1) / (4 * WR_QC);
-    }
-    L.n = (int)(e - s0);
-    if (blk == 0) continue;
-    hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3((unsigned)blk), dim3(256), 0, cur_stream(), L);
-    DPA_CHECK_LAUNCH();
-  }
 }
 
 }  // namespace igemm

@@ -5,6 +5,7 @@
 #include <map>
 
 #include "common.h"
+#include "kernels/handoff.h"
 
 namespace dpa {
 namespace head {
@@ -365,7 +366,7 @@ ce_fwd_rows_kernel(const T* __restrict__ logits, const int64_t* __restrict__ tar
     float tl = 0.f;
 #pragma unroll
     for (int i = 0; i < CE_RT; ++i) tl += red[i];
-    __hip_atomic_store(ws + blockIdx.x, tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through
+    st_wt(ws + blockIdx.x, tl);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned k = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     last_s = k == gridDim.x - 1;
@@ -374,7 +375,7 @@ ce_fwd_rows_kernel(const T* __restrict__ logits, const int64_t* __restrict__ tar
   __syncthreads();
   if (!last_s || tid != 0) return;
   float tl = 0.f;
-  for (int g = 0; g < (int)gridDim.x; ++g) tl += __hip_atomic_load(ws + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int g = 0; g < (int)gridDim.x; ++g) tl += ld_wt(ws + g);
   const float l = cnt > 0.f ? tl / cnt : NAN;
   loss[0] = l;
   if (scale != nullptr) loss[1] = l * sc;

@@ -210,7 +210,7 @@ class WgradBatch:
     a conv whose weight has no ``.grad`` yet (autograd then adopts the returned tensor
     without reading it) keeps its partials in a slab of its own and the reductions of the
     whole pass run in one launch from an end-of-backward callback (csrc/kernels/
-    conv_igemm.hip wgrad_reduce_batch: the same association, bitwise the same gradients),
+    conv_wgrad.hip wgrad_reduce_batch: the same association, bitwise the same gradients),
     before ``backward()`` returns.
 
     Opt-in (DPA_WGRAD_BATCH=1): measured slower on ResNet-50 (14.63 vs 14.52-14.56 ms/step,
