@@ -28,8 +28,14 @@
 // one it is recomputed from x with the forward's exact fma sequence
 // (y > 0  <=>  fma(x, s, b) > 0), so y is neither kept nor re-read.
 // The per-channel statistics are sums around a shift (the running mean, equal
-// on every rank) to avoid E[x^2] - E[x]^2 cancellation.  Deterministic: every
-// reduction has a fixed order (no float atomics).
+// on every rank) to avoid E[x^2] - E[x]^2 cancellation.  That protection holds
+// once the running mean tracks the batch mean: with d = batch mean - shift the
+// fp32 error of the variance grows like u * (d^2 + var) and that of the mean
+// like u * (|d| + std), so a fresh module (running_mean = 0) on data with
+// |mean| >> std has the plain E[x^2] - E[x]^2 conditioning until the running
+// mean has warmed up (tests/test_bn_nhwc_exact_gpu.py, section c, bounds both
+// at 2^-16).  Deterministic: every reduction has a fixed order (no float
+// atomics).
 #include "common.h"
 #include "comm/xgmi.h"
 #include "kernels/handoff.h"
@@ -762,8 +768,11 @@ maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, uint8_t* __restri
     const int n = (int)(p / OH);
     float best[VEC];
     uint8_t bi[VEC];
+    // the index starts at the first in-bounds tap (as ATen): a window of -inf keeps it, and
+    // its gradient goes to a real pixel (tap 0 is padding on the top / left border)
+    const uint8_t first = (uint8_t)((oh == 0 ? 3 : 0) + (ow == 0 ? 1 : 0));
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) { best[j] = -INFINITY; bi[j] = 0; }
+    for (int j = 0; j < VEC; ++j) { best[j] = -INFINITY; bi[j] = first; }
     for (int kh = 0; kh < 3; ++kh) {
       const int ih = 2 * oh - 1 + kh;
       if (ih < 0 || ih >= H) continue;
@@ -1140,6 +1149,7 @@ void avgpool_fwd(at::Tensor x, at::Tensor y, int64_t HW) {
   check_rows(y, N, C);
   dispatch(x, [&](auto tag) {
     typedef decltype(tag) T;
+    TORCH_CHECK(C % V16<T>::N == 0, "avgpool_fwd: channels must be a multiple of ", V16<T>::N);
     hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(elt_grid((long long)N * C / V16<T>::N)), dim3(THR), 0,
                        cur_stream(), dp<T>(x), dp<T>(y), N, (int)HW, C);
   });
@@ -1152,6 +1162,7 @@ void avgpool_bwd(at::Tensor dy, at::Tensor dx, int64_t HW) {
   check_rows(dy, N, C);
   dispatch(dx, [&](auto tag) {
     typedef decltype(tag) T;
+    TORCH_CHECK(C % V16<T>::N == 0, "avgpool_bwd: channels must be a multiple of ", V16<T>::N);
     hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(elt_grid((long long)N * HW * C / V16<T>::N)), dim3(THR), 0,
                        cur_stream(), dp<T>(dy), dp<T>(dx), N, (int)HW, C);
   });

@@ -58,9 +58,11 @@ def test_bn_act_fwd_bwd(C, res, relu, dtype):
                                                   ((16, 1024, 14, 14), False, False, torch.float32),
                                                   ((8, 128, 56, 56), True, False, torch.float32)])
 def test_bn_act_large(shape, res, relu, dtype):
-    """Row counts that use the whole two-level ticket tree (up to 512 row blocks per
-    channel chunk, several chunks) and cumulative-average running stats
-    (momentum=None: num_batches_tracked bumped by the statistics kernel)."""
+    """ResNet-50 row counts, several channel chunks, and cumulative-average running stats
+    (momentum=None: num_batches_tracked bumped by the statistics kernel).  With the default
+    statistics target every shape here has at most 128 row blocks per chunk, which is ONE
+    level of the ticket tree (G1 = 128); the two-level tree is checked against a reference
+    in tests/test_bn_nhwc_exact_gpu.py."""
     from ddp_practice_amd.ops.bn_nhwc import bn_act
 
     torch.manual_seed(2)
