@@ -396,23 +396,25 @@ __device__ __forceinline__ void bn_bwd_coef(const BwdIn<T>& bi, float* coef, flo
 // sink(c, h, w, v00, v01, v10, v11), (h, w) = the window's top-left pixel.
 // ROWS (even): the conv-output rows [r0, r0 + ROWS) of one image (pooled rows
 // [r0/2, r0/2 + ROWS/2), clipped at the image); the sink gets chunk-relative rows.
-template <typename T, int C, int H, int W, int NT_, int ROWS = H>
+// CL: the channels [c0, c0 + CL) of the image's C; the sink gets the channel relative to c0.
+template <typename T, int C, int H, int W, int NT_, int ROWS = H, int CL = C>
 struct BnBwdStage {
   typedef typename Pair2<T>::type P;
   static_assert(ROWS % 2 == 0 && ROWS <= H, "BN-backward staging works on whole 2x2 pooling windows");
   static constexpr int HO = H / 2, WO = W / 2, PP = HO * WO;
-  static constexpr int CHO = ROWS / 2, CPP = CHO * WO, NWIN = C * CPP;  // windows of one chunk
+  static constexpr int CHO = ROWS / 2, CPP = CHO * WO, NWIN = CL * CPP;  // windows of one chunk
   static constexpr int IT = (NWIN + NT_ - 1) / NT_;
   P top[IT], bot[IT];
   T g[IT];
   uint8_t ix[IT];
-  int ho0 = 0;
+  int ho0 = 0, cb0 = 0;
 
-  __device__ __forceinline__ void load(const BwdIn<T>& bi, int b, int r0 = 0) {
+  __device__ __forceinline__ void load(const BwdIn<T>& bi, int b, int r0 = 0, int c0 = 0) {
     ho0 = r0 / 2;
-    const T* yb = bi.y + (size_t)b * C * H * W;
-    const T* dpb = bi.dp + (size_t)b * C * PP;
-    const uint8_t* ib = bi.idx + (size_t)b * C * PP;
+    cb0 = c0;
+    const T* yb = bi.y + ((size_t)b * C + c0) * H * W;
+    const T* dpb = bi.dp + ((size_t)b * C + c0) * PP;
+    const uint8_t* ib = bi.idx + ((size_t)b * C + c0) * PP;
     // unconditional loads (clamped window; emit() skips the out-of-range ones): guarded
     // loads were branched around and waited for group by group (conv2_bwd / wgrad1 .s,
     // scripts/asm_loads.py)
@@ -437,8 +439,9 @@ struct BnBwdStage {
       const int c = e / CPP, pix = e % CPP, hl = pix / WO, wo = pix % WO;
       if (e < NWIN && ho0 + hl < HO) {
         const int ho = hl;  // chunk-relative pooled row
-        const float k1 = coef[c], k2 = coef[C + c], gi = coef[2 * C + c], mean = coef[3 * C + c],
-                    istd = coef[4 * C + c];
+        const int cg = cb0 + c;
+        const float k1 = coef[cg], k2 = coef[C + cg], gi = coef[2 * C + cg], mean = coef[3 * C + cg],
+                    istd = coef[4 * C + cg];
         T v[4];
         __builtin_memcpy(&v[0], &top[i], 2 * sizeof(T));
         __builtin_memcpy(&v[2], &bot[i], 2 * sizeof(T));
@@ -1322,6 +1325,7 @@ bwd_elemt_kernel(const T* __restrict__ dp, const T* __restrict__ p, const uint8_
 // ---------------------------------------------------------------------------
 // Weight/bias gradient partials of the 5x5 conv.  One workgroup per
 // (image, row-chunk); writes wslab[blk][COUT*N + COUT] (dW partial | db partial).
+// (NSL > 0, below: one workgroup per (image, output slice) and one slab row per image.)
 // GEMM: rows = COUT, cols = (ci, kh, kw) natural order, K = pixels of the chunk
 // with the row padded to WP = ceil8(W) (dy is zero in the pad columns).
 // LDS: dy[COUT][ROWS][WP] and 5 kw-shifted copies xs[kw][CIN][ROWS+4][WP] of
@@ -1333,25 +1337,35 @@ bwd_elemt_kernel(const T* __restrict__ dp, const T* __restrict__ p, const uint8_
 // (bin: backward through MaxPool -> ReLU -> BN); needs ROWS == H.
 // WT: the partial row is stored write-through (sc1) for an in-launch reduction
 // (MI355X_MICROARCH.md "Valid forms" row 1; convnet_fused.hip wgrad1_reduce_kernel).
+// NSL > 0: output slices instead of row chunks.  One workgroup per (image b, 16-channel
+// output tile mt, input-channel slice j of NSL) keeps the whole image as its K range
+// (ROWS == H, PRO 2) and writes the 16 x (N / NSL) block [mt*16 .. +16][j*CIN/NSL .. ) of
+// slab row b, so an image yields ONE row [COUT*N + COUT] (blk = (b * COUT/16 + mt) * NSL + j;
+// the j == 0 workgroup writes its tile's 16 bias partials).  It stages only the dy of its
+// 16 output channels and the CIN/NSL input channels of its slice; in the natural
+// [co][ci][kh][kw] order a slice by input channel is one contiguous run per output channel.
 // Dynamic-LDS bytes of conv5x5_wgrad_body<..., DYN = true> (its dy rows, shifted input
 // copies, padded input and staged partial row; the small arrays stay static).
-template <typename T, int CIN, int COUT, int H, int W, int ROWS>
+template <typename T, int CIN, int COUT, int H, int W, int ROWS, int NSL = 0>
 struct WgradLds {
   static constexpr int WP = ceil_to(W, 8), XR = ROWS + 4, WX = WP + 4, N = CIN * 25;
   static constexpr int DYS = ROWS * WP + 8, XCS = XR * WP + 8;
   static constexpr bool DIRECT = ROWS == H, CIF = CIN >= 16;
-  static constexpr size_t DYL = sizeof(T) * (size_t)COUT * DYS;
-  static constexpr size_t XS = sizeof(T) * (size_t)5 * CIN * XCS;
+  static constexpr int CL = NSL > 0 ? 16 : COUT;          // output channels of one workgroup
+  static constexpr int CIS = NSL > 0 ? CIN / NSL : CIN;   // input channels of one workgroup
+  static constexpr int NS = CIS * 25;                     // its GEMM columns
+  static constexpr size_t DYL = sizeof(T) * (size_t)CL * DYS;
+  static constexpr size_t XS = sizeof(T) * (size_t)5 * CIS * XCS;
   static constexpr size_t XPAD = sizeof(T) * (size_t)(DIRECT ? 8 : CIN * XR * WX);
   static constexpr size_t BASE = DYL + XS + XPAD;
-  static constexpr bool STAGE = CIF && BASE + sizeof(float) * (size_t)COUT * N <= 144 * 1024;
+  static constexpr bool STAGE = CIF && BASE + sizeof(float) * (size_t)CL * NS <= 144 * 1024;
   static constexpr size_t o_xs = (DYL + 15) / 16 * 16, o_xpad = (o_xs + XS + 15) / 16 * 16,
                           o_wt = (o_xpad + XPAD + 15) / 16 * 16;
-  static constexpr size_t bytes = o_wt + sizeof(float) * (STAGE ? (size_t)COUT * N : 4);
+  static constexpr size_t bytes = o_wt + sizeof(float) * (STAGE ? (size_t)CL * NS : 4);
 };
 
 template <typename T, int CIN, int COUT, int H, int W, int ROWS, int PRO = 0, bool WT = false, bool CHK = false,
-          bool DYN = false>
+          bool DYN = false, int NSL = 0>
 __device__ __forceinline__ void
 conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ wslab, int nsplit,
                    const BwdIn<T>& bin, const int bid) {
@@ -1364,8 +1378,15 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
   static_assert((ROWS * WP) % 32 == 0, "ROWS*WP must be a multiple of 32");
   constexpr int KSTEPS = ROWS * WP / 32;
   constexpr int N = CIN * 25;
-  constexpr int NTL = (N + 15) / 16;
-  constexpr int MTL = COUT / 16;
+  constexpr bool SL = NSL > 0;  // output slices (one slab row per image), see WgradLds
+  static_assert(!SL || (PRO == 2 && ROWS == H && CIN >= 16 && CIN % NSL == 0 && COUT % 16 == 0 && !WT && !CHK),
+                "output slices: whole image, dy produced on the fly, ci-fastest columns");
+  constexpr int CL = SL ? 16 : COUT;         // output channels staged by this workgroup
+  constexpr int CIS = SL ? CIN / NSL : CIN;  // input channels staged by this workgroup
+  constexpr int NS = CIS * 25;               // its GEMM columns
+  static_assert(!SL || NS % 4 == 0, "a slice leaves as whole 16-B chunks");
+  constexpr int NTL = (NS + 15) / 16;
+  constexpr int MTL = CL / 16;
   constexpr int PAIRS = MTL * NTL;
   constexpr int NW = NTHR / 64;
   constexpr int KSPLIT = PAIRS >= NW ? 1 : NW / PAIRS;  // waves per pair
@@ -1386,8 +1407,9 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
   constexpr bool DIRECT = (ROWS == H);
   __shared__ f32x4 kred[KSPLIT > 1 ? NW : 1][64];
   // the partial row in natural order, staged for whole-chunk stores where LDS allows
-  using WL = WgradLds<T, CIN, COUT, H, W, ROWS>;
+  using WL = WgradLds<T, CIN, COUT, H, W, ROWS, NSL>;
   constexpr bool STAGE = WL::STAGE;
+  static_assert(!SL || STAGE, "output slices leave through the staged tile");
   T* dyl;
   T* xs;
   T* xpad;
@@ -1398,10 +1420,10 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
     xpad = reinterpret_cast<T*>(dpa_dyn_lds + WL::o_xpad);
     wtile = reinterpret_cast<float*>(dpa_dyn_lds + WL::o_wt);
   } else {
-    __shared__ __attribute__((aligned(16))) T dyl_s[COUT * DYS];
-    __shared__ __attribute__((aligned(16))) T xs_s[5 * CIN * XCS];
+    __shared__ __attribute__((aligned(16))) T dyl_s[CL * DYS];
+    __shared__ __attribute__((aligned(16))) T xs_s[5 * CIS * XCS];
     __shared__ __attribute__((aligned(16))) T xpad_s[DIRECT ? 8 : CIN * XR * WX];
-    __shared__ __attribute__((aligned(16))) float wtile_s[STAGE ? COUT * N : 4];
+    __shared__ __attribute__((aligned(16))) float wtile_s[STAGE ? CL * NS : 4];
     dyl = dyl_s;
     xs = xs_s;
     xpad = xpad_s;
@@ -1413,8 +1435,10 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
   DPA_STAMP(0);
   // producer-side check of this workgroup's partial row (BwdIn::chk_row_slot0, common.h)
   const bool rchk = CHK && bin.chk_rows;  // (compiled only where a launch can ask for it)
-  const int r0 = sp * ROWS;
-  const T* xb = x + (size_t)b * CIN * H * W;
+  // output slices: nsplit = (COUT / 16) * NSL workgroups per image, sp = (mt0, sl)
+  const int r0 = SL ? 0 : sp * ROWS;
+  const int mt0 = SL ? sp / (SL ? NSL : 1) : 0, sl = SL ? sp % (SL ? NSL : 1) : 0;
+  const T* xb = x + ((size_t)b * CIN + sl * CIS) * H * W;
   // input rows r0-2 .. r0+ROWS+1 -> xpad interior; all loads issued before the
   // first LDS store (one memory round trip, not one per loop iteration)
   auto stage_xpad = [&]() {
@@ -1444,12 +1468,12 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
   const T zero = Cvt<T>::from_f(0.f);
 
   // dy chunk -> dyl[co][rr][0..WP) (pad columns zero)
-  for (int e = tid; e < COUT * ROWS * (WP - W); e += NTHR) {
+  for (int e = tid; e < CL * ROWS * (WP - W); e += NTHR) {
     const int cr = e / (WP - W), cc = W + e % (WP - W);
     dyl[(cr / ROWS) * DYS + (cr % ROWS) * WP + cc] = zero;
   }
   if (r0 + ROWS > H) {  // rows past the image (last chunk): zero
-    for (int e = tid; e < COUT * ROWS * WP; e += NTHR)
+    for (int e = tid; e < CL * ROWS * WP; e += NTHR)
       if (r0 + (e / WP) % ROWS >= H) dyl[(e / (ROWS * WP)) * DYS + e % (ROWS * WP)] = zero;
   }
   // xs[kw][ci][rr][c] = x[ci][r0 + rr - 2][c + kw - 2] (zero outside the image)
@@ -1457,12 +1481,12 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
 #pragma unroll
     for (int kw = 0; kw < 5; ++kw) {
       const int c = w + 2 - kw;
-      if (c >= 0 && c < WP) xs[(kw * CIN + ci) * XCS + rr * WP + c] = v;
+      if (c >= 0 && c < WP) xs[(kw * CIS + ci) * XCS + rr * WP + c] = v;
     }
   };
   if constexpr (DIRECT) {
-    constexpr int NZ = 5 * CIN * XCS * (int)sizeof(T) / 16;
-    static_assert((5 * CIN * XCS * sizeof(T)) % 16 == 0, "xs must be a whole number of 16-B chunks");
+    constexpr int NZ = 5 * CIS * XCS * (int)sizeof(T) / 16;
+    static_assert((5 * CIS * XCS * sizeof(T)) % 16 == 0, "xs must be a whole number of 16-B chunks");
     uint4* z = reinterpret_cast<uint4*>(xs);
     for (int e = tid; e < NZ; e += NTHR) z[e] = make_uint4(0u, 0u, 0u, 0u);
   } else {
@@ -1476,11 +1500,11 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
   if constexpr (PRO == 2) {
     __shared__ float coef[5 * COUT], sums[2 * COUT];
     __shared__ float part[NTHR];
-    BnBwdStage<T, COUT, H, W, NTHR, ROWS> st;
-    st.load(bin, b, r0);
+    BnBwdStage<T, COUT, H, W, NTHR, ROWS, CL> st;
+    st.load(bin, b, r0, mt0 * 16);
     if constexpr (DIRECT) {
       __syncthreads();  // xs zero-fill before the scatter
-      stage_chw<T, CIN, H, W>(xb, [&](int ci, int h, int ww, T a, T bb) {
+      stage_chw<T, CIS, H, W>(xb, [&](int ci, int h, int ww, T a, T bb) {
         scatter5(ci, h + 2, ww, a);
         scatter5(ci, h + 2, ww + 1, bb);
       });
@@ -1529,7 +1553,7 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
     __syncthreads();
   }
 
-  float* row_out = wslab + (size_t)bid * ROWLEN;
+  float* row_out = wslab + (size_t)(SL ? b : bid) * ROWLEN;
   DPA_STAMP(5);
   const int lane = tid & 63, wv = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
@@ -1538,8 +1562,8 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
   // butterfly: one pass for all channels (a wave-wide reduction per channel
   // cost ~2 us here)
   {
-    constexpr int TPC = NTHR / COUT;
-    static_assert(NTHR % COUT == 0 && TPC <= 64 && (TPC & (TPC - 1)) == 0, "bias-sum lane groups");
+    constexpr int TPC = NTHR / CL;
+    static_assert(NTHR % CL == 0 && TPC <= 64 && (TPC & (TPC - 1)) == 0, "bias-sum lane groups");
     constexpr int E = ROWS * WP;
     static_assert(E % 8 == 0, "dy rows are whole 16-B groups");
     const int co = tid / TPC, sub = tid % TPC;
@@ -1551,8 +1575,8 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
       for (int j = 0; j < 8; ++j) a += Cvt<T>::to_f(e[j]);
     }
     a = group_sum<TPC>(a);  // VALU lane moves (every lane active here)
-    if (sub == 0) {
-      put(&row_out[COUT * N + co], a);
+    if (sub == 0 && sl == 0) {
+      put(&row_out[COUT * N + mt0 * 16 + co], a);
       // the bias column is summed by the AMP step like the weight columns: same row bound
       if (rchk) bin.chk.flag(GradChk::bad(a, bin.chk_row_bound));
     }
@@ -1564,10 +1588,10 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
   for (int pr = pstart; pr < PAIRS; pr += pstep) {
     const int mt = pr / NTL, nt = pr % NTL;
     int n = nt * 16 + r;
-    n = n < N ? n : 0;
-    const int ci = CIF ? n % CIN : n / 25, tap = CIF ? n / CIN : n % 25;
+    n = n < NS ? n : 0;
+    const int ci = CIF ? n % CIS : n / 25, tap = CIF ? n / CIS : n % 25;
     const int kh = tap / 5, kw = tap % 5;
-    const T* brow = &xs[(kw * CIN + ci) * XCS + kh * WP];
+    const T* brow = &xs[(kw * CIS + ci) * XCS + kh * WP];
     const T* arow = &dyl[(mt * 16 + r) * DYS];
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1586,11 +1610,11 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
     }
     // D[row = 4q+i][col = r]: dW[co = mt*16+4q+i][ci][kh][kw] (natural order in the row)
     const int col = nt * 16 + r;
-    if (col < N) {
-      const int nat = CIF ? (col % CIN) * 25 + col / CIN : col;
+    if (col < NS) {
+      const int nat = CIF ? (col % CIS) * 25 + col / CIS : col;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if constexpr (STAGE) wtile[(mt * 16 + 4 * q + i) * N + nat] = acc[i];
+        if constexpr (STAGE) wtile[(mt * 16 + 4 * q + i) * NS + nat] = acc[i];
         else put(&row_out[(mt * 16 + 4 * q + i) * N + nat], acc[i]);
         if (rchk) bin.chk.flag(GradChk::bad(acc[i], bin.chk_row_bound));
       }
@@ -1602,7 +1626,13 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
     // (consecutive lanes, consecutive addresses).
     static_assert((COUT * N) % 4 == 0 && ROWLEN % 4 == 0, "wgrad rows: whole 16-B chunks");
     __syncthreads();
-    if constexpr (WT) {  // 4-B write-through stores, consecutive lanes on consecutive words
+    if constexpr (SL) {  // 16 runs of NS floats: [mt0*16 + rr][sl*CIS ..][kh][kw]
+      for (int e = tid; e < CL * NS / 4; e += NTHR) {
+        const int rr = e / (NS / 4), c4 = e % (NS / 4);
+        *reinterpret_cast<f32x4*>(&row_out[(mt0 * 16 + rr) * N + sl * NS + 4 * c4]) =
+            *reinterpret_cast<const f32x4*>(&wtile[rr * NS + 4 * c4]);
+      }
+    } else if constexpr (WT) {  // 4-B write-through stores, consecutive lanes on consecutive words
       for (int e = tid; e < COUT * N; e += NTHR) put(&row_out[e], wtile[e]);
     } else {
       for (int e = tid; e < COUT * N / 4; e += NTHR)
@@ -1649,6 +1679,56 @@ __device__ __forceinline__ void slab_reduce_body(const float* __restrict__ slab1
     if (chk.word != nullptr) chk.flag(GradChk::bad(t, chk.bound));  // (producer-side check, common.h)
   }
 }
+// As slab_reduce_body for ONE slab, with K chunks of SR_COLS columns per workgroup: a
+// quarter of the workgroups at K = 4, each lane with K independent columns in flight.
+// Per column the association is slab_colsum's (SR_GROUPS row groups, rows g, g + G, ... in
+// that order, partials added in group order): bitwise the same sums.  A lane loads
+// ceil(rows / G) rows where that is <= 2 (the conv2 slab's one row per image at B <= 32)
+// instead of slab_colsum's fixed batch of 16 clamped loads.
+template <int K, int U>
+__device__ __forceinline__ void slab_colsum_chunks(const float* __restrict__ slab, int rows, int n, int c0, int cl,
+                                                   int g, float* v) {
+  constexpr int G = SR_GROUPS;
+  float x[K][U];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const int cc = min(c0 + j * SR_COLS + cl, n - 1);
+#pragma unroll
+    for (int u = 0; u < U; ++u) x[j][u] = slab[(size_t)min(g + u * G, rows - 1) * n + cc];
+  }
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const int cc = min(c0 + j * SR_COLS + cl, n - 1);
+    float a = 0.f;
+#pragma unroll
+    for (int u = 0; u < U; ++u) a += (g + u * G < rows) ? x[j][u] : 0.f;
+    for (int r = g + U * G; r < rows; r += G) a += slab[(size_t)r * n + cc];
+    v[j] = a;
+  }
+}
+template <int K>
+__device__ __forceinline__ void slab_reduce_chunks_body(const float* __restrict__ slab, int rows, int n,
+                                                        float* __restrict__ out, int bid, GradChk chk = GradChk{}) {
+  __shared__ float part[SR_GROUPS][K * SR_COLS + 1];
+  static_assert(K * SR_COLS <= NTHR, "one lane per column in the final sum");
+  if (rows <= 0 || n <= 0) return;
+  const int c0 = bid * K * SR_COLS;
+  const int cl = threadIdx.x % SR_COLS, g = threadIdx.x / SR_COLS;
+  float v[K];
+  if (rows <= 2 * SR_GROUPS) slab_colsum_chunks<K, 2>(slab, rows, n, c0, cl, g, v);
+  else slab_colsum_chunks<K, 16>(slab, rows, n, c0, cl, g, v);
+#pragma unroll
+  for (int j = 0; j < K; ++j) part[g][j * SR_COLS + cl] = v[j];
+  __syncthreads();
+  if (threadIdx.x < K * SR_COLS && c0 + (int)threadIdx.x < n) {
+    float t = 0.f;
+#pragma unroll
+    for (int gg = 0; gg < SR_GROUPS; ++gg) t += part[gg][threadIdx.x];
+    out[c0 + threadIdx.x] = t;
+    if (chk.word != nullptr) chk.flag(GradChk::bad(t, chk.bound));  // (producer-side check, common.h)
+  }
+}
+
 static __global__ void __launch_bounds__(NTHR)
 slab_reduce_kernel(const float* __restrict__ slab1, int rows1, int n1, float* __restrict__ out1,
                    const float* __restrict__ slab2, int rows2, int n2, float* __restrict__ out2) {

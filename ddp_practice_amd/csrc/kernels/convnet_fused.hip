@@ -497,13 +497,48 @@ void conv2_dgrad(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx
 
 // The backward through [BN2 -> ReLU2 -> pool2] feeds two independent products of
 // layer 2: the data grad (-> dp1 + BN1 partial sums, kDgradSplitT<T> workgroups per
-// image) and the weight-grad partials (WG2_ROWS-row chunks).  One launch hosts
-// both roles -- workgroups [0, ndg) the data grad, [ndg, grid) the weight grad --
-// so they overlap on the chip instead of running back to back (each alone fills
-// only 64 / 128 of the 256 CUs at B = 32) and one kernel boundary disappears.
+// image) and the weight-grad partials.  One launch hosts both roles -- workgroups
+// [0, ndg) the data grad, [ndg, grid) the weight grad -- so they overlap on the chip
+// instead of running back to back (each alone fills only 64 / 128 of the 256 CUs at
+// B = 32) and one kernel boundary disappears.
+//
+// The weight-grad role is decomposed by OUTPUT SLICE: a workgroup is (image, 16-channel
+// output tile, input-channel slice of WG2_NSL) with the whole image as its K range
+// (cb::conv5x5_wgrad_body NSL), 2 * WG2_NSL workgroups per image, and an image yields ONE
+// slab row: wslab2 is [B][12832] fp32.  DPA_WG2_NSL=0 builds the row-chunk decomposition
+// instead (WG2_ROWS_-row chunks of one image, every chunk a full 12832-float row: 4 B rows).
+#ifndef DPA_WG2_NSL
+#define DPA_WG2_NSL 2
+#endif
+constexpr int WG2_NSL = DPA_WG2_NSL;
+static_assert(WG2_NSL == 0 || WG2_NSL == 1 || WG2_NSL == 2, "conv2 weight gradient: 0 (row chunks), 1 or 2 slices");
 constexpr int WG2_ROWS_ = 4;
 constexpr int WG1_ROWS_ = 4;
+constexpr int WG2_PER_IMG = WG2_NSL > 0 ? 2 * WG2_NSL : (14 + WG2_ROWS_ - 1) / WG2_ROWS_;
 int64_t wgrad_bn_rows(int64_t layer, int64_t B);
+// workgroups of the conv2 weight-gradient role (its grid share, site grid and residency)
+static int64_t wgrad2_wgs(int64_t B) { return B * WG2_PER_IMG; }
+
+// the conv2 weight-gradient role of one workgroup (bid within the role)
+template <typename T, bool DYN>
+__device__ __forceinline__ void conv2_wgrad_role(const T* __restrict__ p1, float* __restrict__ wslab2,
+                                                 const BwdIn<T>& bi_w, int bid) {
+  if constexpr (WG2_NSL > 0)
+    cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, 14, 2, false, false, DYN, WG2_NSL>(p1, nullptr, wslab2, WG2_PER_IMG,
+                                                                                bi_w, bid);
+  else
+    cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, WG2_ROWS_, 2, false, false, DYN>(p1, nullptr, wslab2, WG2_PER_IMG,
+                                                                              bi_w, bid);
+}
+template <typename T>
+constexpr size_t conv2_wgrad_lds() {
+  return cb::WgradLds<T, 16, 32, 14, 14, (WG2_NSL > 0 ? 14 : WG2_ROWS_), WG2_NSL>::bytes;
+}
+template <typename T>
+__global__ void __launch_bounds__(cb::NTHR)
+conv2_wgrad_kernel(const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w) {
+  conv2_wgrad_role<T, false>(p1, wslab2, bi_w, (int)blockIdx.x);
+}
 // fc weight / bias gradient of the per-image head (csrc/kernels/convnet_head.hip): the head's
 // one reduction over the batch, computed by extra workgroups of the conv2 backward launch
 // (which needs none of it) instead of on the head's critical path:
@@ -586,13 +621,12 @@ template <typename T>
 __global__ void __launch_bounds__(cb::NTHR)
 conv2_bwd_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d, BwdEpi<T> ep,
                  const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int ndg, int nwg, FcW<T> fw) {
-  constexpr int nsw = (14 + WG2_ROWS_ - 1) / WG2_ROWS_;
   const int bid = (int)blockIdx.x;
   if (bid < ndg)
     cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1>(nullptr, nullptr, nullptr, dp1, nullptr, nullptr, nullptr,
                                                     kDgradSplitT<T>, PoolIn<T>{}, bi_d, ep, wpk_d, cb::WPack<T>{}, bid);
   else if (bid < ndg + nwg)
-    cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, WG2_ROWS_, 2>(p1, nullptr, wslab2, nsw, bi_w, bid - ndg);
+    conv2_wgrad_role<T, false>(p1, wslab2, bi_w, bid - ndg);
   else
     fc_wgrad_body<T>(fw, bid - ndg - nwg);
 }
@@ -608,22 +642,20 @@ __global__ void __launch_bounds__(cb::NTHR)
 conv2_bwd_dyn_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d, BwdEpi<T> ep,
                      const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int ndg, int nwg,
                      FcW<T> fw) {
-  constexpr int nsw = (14 + WG2_ROWS_ - 1) / WG2_ROWS_;
   const int bid = (int)blockIdx.x;
   if (bid < ndg)
     cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1, true>(nullptr, nullptr, nullptr, dp1, nullptr, nullptr, nullptr,
                                                           kDgradSplitT<T>, PoolIn<T>{}, bi_d, ep, wpk_d,
                                                           cb::WPack<T>{}, bid);
   else if (bid < ndg + nwg)
-    cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, WG2_ROWS_, 2, false, false, true>(p1, nullptr, wslab2, nsw, bi_w,
-                                                                                bid - ndg);
+    conv2_wgrad_role<T, true>(p1, wslab2, bi_w, bid - ndg);
   else
     fc_wgrad_body<T>(fw, bid - ndg - nwg);
 }
 
 template <typename T>
 constexpr size_t conv2_bwd_dyn_bytes() {
-  return std::max(cb::conv5x5_dyn_bytes<T, 32, 16, 14, 14>(), cb::WgradLds<T, 16, 32, 14, 14, WG2_ROWS_>::bytes);
+  return std::max(cb::conv5x5_dyn_bytes<T, 32, 16, 14, 14>(), conv2_wgrad_lds<T>());
 }
 
 // DPA_FP32_MERGED_BWD=0: the two fp32 launches below (A/B runs)
@@ -662,10 +694,9 @@ static bool lp_dyn_bwd() {
 template <typename T>
 __global__ void __launch_bounds__(cb::NTHR)
 conv2_wgrad_fc_kernel(const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int nwg, FcW<T> fw) {
-  constexpr int nsw = (14 + WG2_ROWS_ - 1) / WG2_ROWS_;
   const int bid = (int)blockIdx.x;
   if (bid < nwg)
-    cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, WG2_ROWS_, 2>(p1, nullptr, wslab2, nsw, bi_w, bid);
+    conv2_wgrad_role<T, false>(p1, wslab2, bi_w, bid);
   else
     fc_wgrad_body<T>(fw, bid - nwg);
 }
@@ -737,8 +768,8 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
   TORCH_CHECK(dg2.has_value() == dbe2.has_value(), "conv2_bwd: dg2 and dbe2 go together");
   if (dg2.has_value()) TORCH_CHECK(dg2->numel() == 32 && dbe2->numel() == 32 && dg2->scalar_type() == at::kFloat);
   if (xc) TORCH_CHECK(!lsum2.has_value(), "fused SyncBN exchange: gsum2 must be this rank's rows (no lsum2)");
-  const int ndg = B * dgrad_split(y2.scalar_type() == at::kFloat), nwg = (int)wgrad_bn_rows(2, B);
-  TORCH_CHECK(wslab2.numel() == (int64_t)nwg * (32 * 400 + 32), "wgrad slab size");
+  const int ndg = B * dgrad_split(y2.scalar_type() == at::kFloat), nwg = (int)wgrad2_wgs(B);
+  TORCH_CHECK(wslab2.numel() == wgrad_bn_rows(2, B) * (32 * 400 + 32), "wgrad slab size");
   if (B == 0) return;
   with_t(dt_of(y2), [&](auto tag) {
     typedef decltype(tag) T;
@@ -787,13 +818,14 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
 
 // [pool/ReLU/BN backward of the block whose conv is (CIN->COUT, HxW)] -> weight-grad partials.
 // layer 2: x = p1 [B,16,14,14], (y, dp, idx) = layer-2 tensors; layer 1: x = images, layer-1 tensors.
-// Weight-gradient row chunks (BN backward applied on the fly per chunk): more,
-// shorter workgroups than one image each (B = 32 -> 32 workgroups for 256 CUs).
+// Layer 1: weight-gradient row chunks (BN backward applied on the fly per chunk): more,
+// shorter workgroups than one image each (B = 32 -> 32 workgroups for 256 CUs), one slab
+// row per chunk.  Layer 2: output slices of whole images (conv2_wgrad_role above), one
+// slab row per image.  wgrad_bn_rows: the ROWS of a layer's slab (what its consumers sum).
 constexpr int WG1_ROWS = WG1_ROWS_;  // layer 1 (28 rows): 7 chunks per image
-constexpr int WG2_ROWS = WG2_ROWS_;  // layer 2 (14 rows): 4 chunks per image (last one 2 rows)
 int64_t wgrad_bn_rows(int64_t layer, int64_t B) {
   TORCH_CHECK(layer == 1 || layer == 2);
-  return B * (layer == 1 ? (28 + WG1_ROWS - 1) / WG1_ROWS : (14 + WG2_ROWS - 1) / WG2_ROWS);
+  return B * (layer == 1 ? (28 + WG1_ROWS - 1) / WG1_ROWS : (WG2_NSL > 0 ? 1 : WG2_PER_IMG));
 }
 
 void conv_wgrad_bn(at::Tensor x, at::Tensor y, at::Tensor dp, at::Tensor idx, at::Tensor fstats, at::Tensor gsum,
@@ -812,10 +844,9 @@ void conv_wgrad_bn(at::Tensor x, at::Tensor y, at::Tensor dp, at::Tensor idx, at
       bi.xs = site_of(xc, cout == 32 ? xgmi::kSiteBwd2Wgrad : xgmi::kSiteBwd1);
     }
     if (cin == 16 && cout == 32 && H == 14) {
-      constexpr int ns = (14 + WG2_ROWS - 1) / WG2_ROWS;
-      TORCH_CHECK(wslab.numel() == (int64_t)B * ns * (32 * 400 + 32), "wgrad slab size");
-      hipLaunchKernelGGL((cb::conv5x5_wgrad_kernel<T, 16, 32, 14, 14, WG2_ROWS, 2>), dim3(B * ns), dim3(cb::NTHR),
-                         0, cur_stream(), dptr<T>(x), nullptr, wslab.data_ptr<float>(), ns, bi);
+      TORCH_CHECK(wslab.numel() == wgrad_bn_rows(2, B) * (32 * 400 + 32), "wgrad slab size");
+      hipLaunchKernelGGL(conv2_wgrad_kernel<T>, dim3((int)wgrad2_wgs(B)), dim3(cb::NTHR), 0, cur_stream(),
+                         dptr<T>(x), wslab.data_ptr<float>(), bi);
     } else if (cin == 1 && cout == 16 && H == 28) {
       constexpr int ns = (28 + WG1_ROWS - 1) / WG1_ROWS;
       TORCH_CHECK(wslab.numel() == (int64_t)B * ns * (16 * 25 + 16), "wgrad slab size");
@@ -965,7 +996,13 @@ void wgrad1_reduce(at::Tensor x, at::Tensor y1, at::Tensor dp1, at::Tensor idx1,
 // column sums of the conv2 weight-grad slab into [dW2 | db2] (independent work that
 // fills the CUs the 224 conv1 workgroups leave idle).  The conv1 slab's own column
 // sums are left to the consumer: the fused AMP-SGD launch (optim.hip SlabSrc) or a
-// slab_reduce launch.
+// slab_reduce launch.  A reduction workgroup owns SLAB2_K chunks of 16 columns (the conv2
+// slab has one row per image: few rows per lane, so more columns per lane instead);
+// DPA_SLAB2_CHUNKS=1: one chunk each (cb::slab_reduce_body), the same sums bitwise.
+#ifndef DPA_SLAB2_CHUNKS
+#define DPA_SLAB2_CHUNKS 4
+#endif
+constexpr int SLAB2_K = DPA_SLAB2_CHUNKS;
 template <typename T>
 __global__ void __launch_bounds__(cb::NTHR)
 wgrad1_slab2_kernel(const T* __restrict__ x, float* __restrict__ wslab1, BwdIn<T> bi, int nwg1,
@@ -973,6 +1010,8 @@ wgrad1_slab2_kernel(const T* __restrict__ x, float* __restrict__ wslab1, BwdIn<T
   constexpr int ns = (28 + WG1_ROWS_ - 1) / WG1_ROWS_;
   if ((int)blockIdx.x < nwg1)
     cb::conv5x5_wgrad_body<T, 1, 16, 28, 28, WG1_ROWS_, 2, false, true>(x, nullptr, wslab1, ns, bi, (int)blockIdx.x);
+  else if constexpr (SLAB2_K > 1)
+    cb::slab_reduce_chunks_body<SLAB2_K>(wslab2, rows2, n2, out2, (int)blockIdx.x - nwg1, rc);
   else
     cb::slab_reduce_body(nullptr, 0, 0, nullptr, wslab2, rows2, n2, out2, (int)blockIdx.x - nwg1, rc);
 }
@@ -990,7 +1029,7 @@ void conv1_wgrad_slab2(at::Tensor x, at::Tensor y1, at::Tensor dp1, at::Tensor i
   TORCH_CHECK(wslab1.numel() == (int64_t)nwg1 * N1, "conv1_wgrad_slab2: conv1 slab size");
   TORCH_CHECK(wslab2.numel() == (int64_t)rows2 * N2 && out2.numel() == N2, "conv1_wgrad_slab2: conv2 slab sizes");
   if (B == 0) return;
-  const int nred = (N2 + cb::SR_COLS - 1) / cb::SR_COLS;
+  const int nred = (N2 + SLAB2_K * cb::SR_COLS - 1) / (SLAB2_K * cb::SR_COLS);
   with_t(dt_of(y1), [&](auto tag) {
     typedef decltype(tag) T;
     BwdIn<T> bi = bwd_in<T>(dp1, idx1, y1, fstats1, gsum, lsum, g1, eps1, 16, dg1, dbe1);
@@ -1167,7 +1206,7 @@ void convnet_amp_step(std::vector<at::Tensor> params, std::vector<at::Tensor> gr
 bool sites_resident(int64_t B, at::ScalarType st) {
   // every site launch must also fit its site's epoch words (comm/xgmi.h set_site_grid):
   // the conv1 weight gradient's 7 B workgroups pass kEpochWords at B >= 74
-  bool ok = xgmi::site_grid_fits(wgrad_bn_rows(1, B)) && xgmi::site_grid_fits(wgrad_bn_rows(2, B)) &&
+  bool ok = xgmi::site_grid_fits(wgrad_bn_rows(1, B)) && xgmi::site_grid_fits(wgrad2_wgs(B)) &&
             xgmi::site_grid_fits(B * dgrad_split(st == at::kFloat)) &&
             xgmi::site_grid_fits(fwd2_split(st == at::kFloat) * B);
   auto chk = [&](const void* k, int64_t grid) { ok = ok && co_resident(k, (int)grid, cb::NTHR, 0); };
@@ -1181,16 +1220,15 @@ bool sites_resident(int64_t B, at::ScalarType st) {
     if constexpr (!std::is_same<T, float>::value) {
       if (lp_dyn_bwd())
         ok = ok && co_resident(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<T>),
-                               (int)(B * kDgradSplitT<T> + wgrad_bn_rows(2, B) + FC_BLOCKS), cb::NTHR,
+                               (int)(B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS), cb::NTHR,
                                conv2_bwd_dyn_bytes<T>());
       else
-        chk(reinterpret_cast<const void*>(&conv2_bwd_kernel<T>), B * kDgradSplitT<T> + wgrad_bn_rows(2, B) + FC_BLOCKS);
+        chk(reinterpret_cast<const void*>(&conv2_bwd_kernel<T>), B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS);
     } else if (fp32_merged_bwd())
       ok = ok && co_resident(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<T>),
-                             (int)(B * kDgradSplitT<T> + wgrad_bn_rows(2, B) + FC_BLOCKS), cb::NTHR,
+                             (int)(B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS), cb::NTHR,
                              conv2_bwd_dyn_bytes<T>());
-    chk(reinterpret_cast<const void*>(&cb::conv5x5_wgrad_kernel<T, 16, 32, 14, 14, WG2_ROWS, 2>),
-        wgrad_bn_rows(2, B));
+    chk(reinterpret_cast<const void*>(&conv2_wgrad_kernel<T>), wgrad2_wgs(B));
     chk(reinterpret_cast<const void*>(&cb::conv5x5_wgrad_kernel<T, 1, 16, 28, 28, WG1_ROWS, 2>),
         wgrad_bn_rows(1, B));
     chk(reinterpret_cast<const void*>(&wgrad1_reduce_kernel<T>), wgrad_bn_rows(1, B));
