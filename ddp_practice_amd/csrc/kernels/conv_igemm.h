@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <initializer_list>
+#include <mutex>
 #include <tuple>
 #include <type_traits>
 #include <vector>
@@ -104,6 +105,45 @@ bool for_variant(std::tuple<V...>, F&& f) {
   return (f(V{}) || ...);
 }
 
+// Which variants the last conv_fwd / conv_wgrad call launched (host bookkeeping only, read by
+// the last_launch() binding: the tests assert the variant a case was designed to reach).
+// A call launches at most a conv kernel and a statistics-tree kernel.  Forward and backward
+// calls come from different threads (autograd's device thread): one lock around the record.
+struct LaunchRec {
+  const char* family;
+  const char* dtype;
+  int n;
+  int v[8];
+};
+struct LaunchLog {
+  std::mutex mu;
+  int n = 0;
+  LaunchRec rec[2];
+  void clear() {
+    std::lock_guard<std::mutex> lk(mu);
+    n = 0;
+  }
+};
+LaunchLog& launch_log();  // conv_igemm.hip
+template <typename V>
+inline void note_launch(const char* family, const char* dtype) {
+  static_assert(V::n <= 8, "LaunchRec holds 8 template arguments");
+  LaunchLog& L = launch_log();
+  std::lock_guard<std::mutex> lk(L.mu);
+  if (L.n >= 2) return;
+  LaunchRec& r = L.rec[L.n++];
+  r.family = family;
+  r.dtype = dtype;
+  r.n = V::n;
+  std::copy(V::v, V::v + V::n, r.v);
+}
+// the template arguments of every variant of a list, generated from the tuple itself
+template <typename... V>
+std::vector<std::vector<int64_t>> variant_list(std::tuple<V...>) {
+  return {std::vector<int64_t>(V::v, V::v + V::n)...};
+}
+inline const char* dtype_name(const at::Tensor& t) { return t.scalar_type() == at::kBFloat16 ? "bf16" : "f16"; }
+
 inline Geom geom(const at::Tensor& x, const at::Tensor& w, int stride, int pad) {
   // x: [N, C, H, W] channels_last; w: [K, C, R, S] channels_last (= [K][R][S][C] in memory)
   Geom g;
@@ -123,6 +163,7 @@ int64_t wgrad_config(int64_t glds);
 int64_t wgrad_waves_config(int64_t w);
 int64_t wgrad_fixup_config(int64_t maxsp);
 int64_t wgrad_splits(int64_t M, int64_t K, int64_t C, int64_t R, int64_t S);
+std::vector<std::vector<int64_t>> wgrad_variants(bool glds);  // WgradVariants / WgradGldsVariants
 std::vector<int64_t> conv_wgrad(at::Tensor dy, at::Tensor x, at::Tensor grad, int64_t stride, int64_t pad,
                                 at::Tensor slab, int64_t mode, bool reduce);
 void wgrad_reduce_batch(std::vector<at::Tensor> slabs, std::vector<at::Tensor> grads,

@@ -24,6 +24,9 @@
 //   * XCD-aware workgroup order (the channel tiles of one pixel tile share an L2);
 //   * the pixel tile's im2col addresses (n, ih0, iw0) are computed once per
 //     workgroup; padding / ragged M are zero-filled in the loader.
+#include <map>
+#include <string>
+
 #include "comm/xgmi.h"
 #include "kernels/conv_igemm.h"
 
@@ -137,7 +140,9 @@ __device__ __forceinline__ void stage_tile(T* tile, const f32x4 (&acc)[CT][PT], 
 }
 
 // Output stores: whole 16-B chunks, consecutive lanes along a pixel's channels;
-// y (+)= tile (+ aux at the even pixels), summed in fp32, rounded once.  MODE_S2T writes
+// y (+)= tile (+ aux at the even pixels): the tile comes from LDS already rounded to T
+// (stage_tile), old + aux + tile is summed in fp32 and rounded again -- two roundings on
+// the accumulate / aux paths, one otherwise.  MODE_S2T writes
 // parity class (py, px) with stride 2.  OLDPRE: the accumulated-onto chunk of pass `it` was
 // prefetched by the kernel (old_of(it)) instead of being read here; stored(it, raw) sees
 // every stored chunk (the BN-backward sums of conv_glds_kernel).
@@ -1001,6 +1006,11 @@ void pack_weights(at::Tensor table, int64_t n, int64_t tiles, int64_t dtype_code
   DPA_CHECK_LAUNCH();
 }
 
+LaunchLog& launch_log() {
+  static LaunchLog log;
+  return log;
+}
+
 static int tile_n(int64_t K) { return K % 128 == 0 ? 128 : 64; }
 
 // 1x1 convs on conv_glds_kernel (DPA_G1X1=0: the general kernel, A/B runs); its pixel tile
@@ -1092,6 +1102,7 @@ static void launch_stat_tree(StatArgs sa, long long M, int bm, int K, int BN) {
     found = for_variant(Sum1Variants{}, [&](auto v) {
       using V = decltype(v);
       if (!V::is({BN, NL})) return false;
+      note_launch<V>("stat_sum1", "f32");
       hipLaunchKernelGGL((stat_sum1_kernel<V::v[0], V::v[1]>), gr, dim3(S1_THR), 0, cur_stream(), sa, M, bm, K);
       return true;
     });
@@ -1101,6 +1112,7 @@ static void launch_stat_tree(StatArgs sa, long long M, int bm, int K, int BN) {
     found = for_variant(TreeVariants{}, [&](auto v) {
       using V = decltype(v);
       if (!V::is({BN})) return false;
+      note_launch<V>("stat_tree", "f32");
       hipLaunchKernelGGL(stat_tree_kernel<V::v[0]>, dim3((unsigned)(NG * (K / BN))), dim3(THR), 0, cur_stream(), sa, M,
                          bm, K);
       return true;
@@ -1169,6 +1181,8 @@ void conv_fwd(at::Tensor x, at::Tensor w, at::Tensor y, int64_t stride, int64_t 
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) && w.is_contiguous(at::MemoryFormat::ChannelsLast) &&
                   y.is_contiguous(at::MemoryFormat::ChannelsLast),
               "conv_fwd: channels_last x / w / y");
+  launch_log().clear();
+  const char* dn = dtype_name(x);
   Geom g = geom(x, w, (int)stride, (int)pad);
   g.accumulate = accumulate ? 1 : 0;
   TORCH_CHECK(mode == MODE_GEN || mode == MODE_STEM || mode == MODE_S2T, "conv_fwd: mode");
@@ -1301,6 +1315,7 @@ void conv_fwd(at::Tensor x, at::Tensor w, at::Tensor y, int64_t stride, int64_t 
       return for_variant(GldsVariants{}, [&](auto v) {
         using V = decltype(v);
         if (!V::is({BP, BN, BS, kxk, NS, NWP, NWC})) return false;
+        note_launch<V>("glds", dn);
         hipLaunchKernelGGL((conv_glds_kernel<T, V::v[0], V::v[1], V::v[2], V::v[3] != 0, V::v[4], V::v[5], V::v[6]>),
                            dim3((unsigned)blocks), dim3(64 * NWP * NWC), 0, cur_stream(),
                            reinterpret_cast<const T*>(x.data_ptr()), reinterpret_cast<const T*>(w.data_ptr()),
@@ -1326,6 +1341,7 @@ void conv_fwd(at::Tensor x, at::Tensor w, at::Tensor y, int64_t stride, int64_t 
     return for_variant(FwdVariants{}, [&](auto v) {
       using V = decltype(v);
       if (!V::is({BN, (int)mode})) return false;
+      note_launch<V>("fwd", dn);
       hipLaunchKernelGGL((conv_fwd_kernel<T, V::v[0], V::v[1]>), dim3((unsigned)blocks), dim3(THR), 0, cur_stream(),
                          reinterpret_cast<const T*>(x.data_ptr()), reinterpret_cast<const T*>(w.data_ptr()),
                          reinterpret_cast<T*>(y.data_ptr()), sa, g);
@@ -1336,6 +1352,22 @@ void conv_fwd(at::Tensor x, at::Tensor w, at::Tensor y, int64_t stride, int64_t 
   TORCH_CHECK(found, "conv_fwd: no kernel variant for ", BN, "-channel tiles, mode ", mode);
   DPA_CHECK_LAUNCH();
   if (sa.defer) launch_stat_tree(sa, g.M, BM, (int)g.K, BN);
+}
+
+// [(family, template arguments, dtype)] of the kernels the last conv_fwd / conv_wgrad call launched
+static std::vector<std::tuple<std::string, std::vector<int64_t>, std::string>> last_launch() {
+  std::vector<std::tuple<std::string, std::vector<int64_t>, std::string>> out;
+  LaunchLog& L = launch_log();
+  std::lock_guard<std::mutex> lk(L.mu);
+  for (int i = 0; i < L.n; ++i)
+    out.emplace_back(L.rec[i].family, std::vector<int64_t>(L.rec[i].v, L.rec[i].v + L.rec[i].n), L.rec[i].dtype);
+  return out;
+}
+// family -> the template arguments of every instantiated variant (from the dispatch tuples)
+static std::map<std::string, std::vector<std::vector<int64_t>>> variants() {
+  return {{"fwd", variant_list(FwdVariants{})},        {"glds", variant_list(GldsVariants{})},
+          {"stat_sum1", variant_list(Sum1Variants{})}, {"stat_tree", variant_list(TreeVariants{})},
+          {"wgrad", wgrad_variants(false)},            {"wgrad_glds", wgrad_variants(true)}};
 }
 
 }  // namespace igemm
@@ -1352,6 +1384,8 @@ void register_conv_igemm(pybind11::module& m) {
         pybind11::arg("bn_beta") = pybind11::none(), pybind11::arg("bn_out") = pybind11::none(),
         pybind11::arg("bn_dgamma") = pybind11::none(), pybind11::arg("bn_dbeta") = pybind11::none(),
         pybind11::arg("xc") = pybind11::none());
+  s.def("last_launch", &igemm::last_launch);
+  s.def("variants", &igemm::variants);
   s.def("supported", &igemm::supported);
   s.def("stat_part_len", &igemm::stat_part_len);
   s.def("stat_tickets_len", &igemm::stat_tickets_len);

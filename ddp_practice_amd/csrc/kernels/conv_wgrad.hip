@@ -461,6 +461,10 @@ using WgradGldsVariants =
                Var<128, 128, 2, 4, 0>, Var<128, 64, 4, 2, 0>, Var<64, 128, 2, 4, 0>, Var<64, 64, 2, 4, 0>,
                Var<128, 128, 2, 2, 0>, Var<128, 64, 2, 2, 0>, Var<64, 128, 2, 2, 0>, Var<64, 64, 2, 2, 0>>;
 
+std::vector<std::vector<int64_t>> wgrad_variants(bool glds) {
+  return glds ? variant_list(WgradGldsVariants{}) : variant_list(WgradVariants{});
+}
+
 // dy: [N, K, OH, OW] channels_last; x: [N, C, H, W] channels_last; grad: fp32 [K, C, R, S]
 // contiguous (written, not accumulated); slab: fp32 >= splits * K * R*S*C.
 // mode MODE_STEM: x = the stem_pack image [N, 4, H, W], grad [K, 3, 7, 7] (stride 2, pad 3).
@@ -474,6 +478,8 @@ std::vector<int64_t> conv_wgrad(at::Tensor dy, at::Tensor x, at::Tensor grad, in
   TORCH_CHECK(grad.scalar_type() == at::kFloat && grad.is_contiguous() && grad.dim() == 4, "conv_wgrad: fp32 grad");
   const bool stem = mode == MODE_STEM;
   TORCH_CHECK(mode == MODE_GEN || stem, "conv_wgrad: mode");
+  launch_log().clear();
+  const char* dn = dtype_name(x);
   Geom g = geom(x, grad, (int)stride, (int)pad);
   int Cd = g.C, Rd = g.R, Sd = g.S;  // gradient dims (the stem's padded K space drops to these)
   if (stem) {
@@ -512,6 +518,7 @@ std::vector<int64_t> conv_wgrad(at::Tensor dy, at::Tensor x, at::Tensor grad, in
       return for_variant(WgradGldsVariants{}, [&](auto v) {
         using V = decltype(v);
         if (!V::is({BM, BN, NWM, NWN, fixed})) return false;
+        note_launch<V>("wgrad_glds", dn);
         hipLaunchKernelGGL((conv_wgrad_glds_kernel<T, V::v[0], V::v[1], V::v[2], V::v[3], V::v[4] != 0>), gr,
                            dim3(64 * NWM * NWN), 0, cur_stream(), dp, xp, sl, g, (int)sp, pps, grad.data_ptr<float>(), tk);
         return true;
@@ -519,6 +526,7 @@ std::vector<int64_t> conv_wgrad(at::Tensor dy, at::Tensor x, at::Tensor grad, in
     return for_variant(WgradVariants{}, [&](auto v) {
       using V = decltype(v);
       if (!V::is({BM, BN, stem ? MODE_STEM : MODE_GEN})) return false;
+      note_launch<V>("wgrad", dn);
       hipLaunchKernelGGL((conv_wgrad_kernel<T, V::v[0], V::v[1], V::v[2]>), gr, dim3(THR), 0, cur_stream(), dp, xp, sl,
                          g, (int)sp, pps);
       return true;

@@ -89,9 +89,9 @@ def test_conv_ops_fwd_bwd_with_stats(C, shape):
 @pytest.mark.parametrize("shape", [
     (2, 64, 14, 14, 64, 3, 1, 1),     # 64 x 576: BM=64, BN=64
     (2, 128, 15, 15, 128, 3, 2, 1),   # stride 2, odd input
-    (3, 256, 7, 7, 128, 1, 1, 0),     # 1x1, ragged pixel count
+    (3, 256, 7, 7, 128, 1, 1, 0),     # 1x1, ragged pixel count (M = 147 < 1024: one split)
     (2, 128, 14, 14, 256, 1, 2, 0),   # 1x1 s2 projection
-    (4, 64, 28, 28, 128, 3, 1, 1),    # several pixel splits
+    (4, 64, 28, 28, 128, 3, 1, 1),    # several pixel splits (6 of 576 pixels, the last 256: whole steps)
 ])
 def test_conv_wgrad_matches_torch(C, dtype, shape):
     from ddp_practice_amd.ops.conv_igemm import conv_wgrad
@@ -280,7 +280,7 @@ def test_conv_fwd_deferred_statistics(C, shape, defer_min):
 @pytest.mark.parametrize("shape", [
     (2, 64, 14, 14, 64, 3, 1, 1),     # 3x3: padding taps read the zero page
     (2, 128, 15, 15, 128, 3, 2, 1),   # stride 2, odd input
-    (3, 256, 7, 7, 128, 1, 1, 0),     # 1x1, ragged pixel count (split past the end)
+    (3, 256, 7, 7, 128, 1, 1, 0),     # 1x1, ragged pixel count (M = 147 < 1024: one split)
     (2, 128, 14, 14, 256, 1, 2, 0),   # 1x1 stride 2
     (4, 64, 28, 28, 128, 3, 1, 1),    # several pixel splits
 ])
@@ -311,7 +311,7 @@ def test_conv_wgrad_glds_matches_register_staged(C, shape):
 
 @pytest.mark.parametrize("shape", [
     (2, 64, 14, 14, 64, 3, 1, 1),     # 3x3, one tile x splits
-    (3, 256, 7, 7, 128, 1, 1, 0),     # 1x1, ragged pixel count (split past the end)
+    (3, 256, 7, 7, 128, 1, 1, 0),     # 1x1, ragged pixel count (M = 147 < 1024: one split)
     (2, 128, 14, 14, 256, 1, 2, 0),   # 1x1 stride 2
     (4, 64, 28, 28, 128, 3, 1, 1),    # several pixel splits
     (8, 256, 14, 14, 512, 1, 1, 0),   # 4 x 2 tiles
