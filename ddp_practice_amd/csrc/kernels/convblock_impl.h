@@ -47,11 +47,54 @@ __host__ __device__ constexpr int fslab_row(int C) { return 2 * C + 1; }
 
 template <int I> struct SH;
 template <> struct SH<0> { static constexpr int CIN = 1, COUT = 16, H = 28, W = 28, SPLIT = 4, WROWS = 28; };
-#ifndef DPA_FWD2_SPLIT
-#define DPA_FWD2_SPLIT 2  // workgroups per image of the conv2 forward (experiment builds: -DDPA_FWD2_SPLIT=4)
-#endif
-template <> struct SH<1> { static constexpr int CIN = 16, COUT = 32, H = 14, W = 14, SPLIT = DPA_FWD2_SPLIT, WROWS = 14; };
+template <> struct SH<1> { static constexpr int CIN = 16, COUT = 32, H = 14, W = 14, SPLIT = 2, WROWS = 14; };
 constexpr int kBwdSplit = 8;  // batch split of bwd_reduce
+
+// Workgroups per image of the FUSED conv2 forward (convnet_fused.hip conv2_fwd; the per-layer
+// op above keeps SH<1>::SPLIT), per storage type.  Here because its consumer, the head's BN2
+// finalize (convnet_head.hip), sizes its one load batch by the slab's B * split rows.
+// 4 for every type: with row windows (conv5x5_body WR) a quarter's 9 input rows are ONE staging
+// iteration per lane where a half's 10 need two, and each wave runs one m-tile instead of two;
+// bf16 step 0.0426 -> 0.0409 ms (profiles/conv2_rowwin_ab.txt; with every split staging the
+// whole image, 4 was 0.6 us slower: r6m_split_ab.txt).
+// Experiment builds: -DDPA_FWD2_SPLIT=2|4 (bf16 / fp16), -DDPA_FWD2_SPLIT_F32=...
+#ifndef DPA_FWD2_SPLIT
+#define DPA_FWD2_SPLIT 4
+#endif
+#ifndef DPA_FWD2_SPLIT_F32
+#define DPA_FWD2_SPLIT_F32 4
+#endif
+template <typename T>
+constexpr int kFwd2SplitT = sizeof(T) == 4 ? DPA_FWD2_SPLIT_F32 : DPA_FWD2_SPLIT;
+
+// Row-window staging of conv5x5_body (its WR parameter): the most input rows any of the nsplit
+// workgroups of an H x W image stages.  Workgroup sp computes the output pixels of m-tiles
+// [MT*sp/nsplit, MT*(sp+1)/nsplit) and reads their rows plus the two halo rows each side,
+// clipped to the image; `even`: rounded out to whole 2x2 pooling windows (PRO 2).
+// 0: some split is empty (nsplit > MT).
+__host__ __device__ constexpr int conv5x5_win_rows(int H, int W, int nsplit, bool even) {
+  const int HW = H * W, MT = (HW + 15) / 16;
+  int mx = 0;
+  for (int sp = 0; sp < nsplit; ++sp) {
+    const int p0 = 16 * (MT * sp / nsplit), p1e = 16 * (MT * (sp + 1) / nsplit), p1 = p1e < HW ? p1e : HW;
+    if (p1 <= p0) return 0;
+    int lo = p0 / W - 2, hi = (p1 - 1) / W + 2;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > H - 1 ? H - 1 : hi;
+    if (even) {
+      lo &= ~1;
+      hi |= 1;
+    }
+    mx = hi - lo + 1 > mx ? hi - lo + 1 : mx;
+  }
+  return mx;
+}
+// DPA_CONV2_WHOLE_IMAGE: the fused conv2 kernels stage the whole image in every split (A/B builds)
+#ifdef DPA_CONV2_WHOLE_IMAGE
+constexpr bool kConv2RowWindow = false;
+#else
+constexpr bool kConv2RowWindow = true;
+#endif
 
 // ---------------------------------------------------------------------------
 // Staging helpers.  Every global->LDS staging loop is split into "issue every
@@ -139,8 +182,10 @@ struct BNParams {
 // lane are loaded in ONE batch (all loads in flight before the first add), so
 // a slab of up to RSUM_U * G rows costs one L2 round trip instead of one per
 // 4 rows (the partial-sum slabs are 64-256 rows: this was 3-5 serial trips).
+// U: the batch size, a template parameter (RSUM_U unless the caller knows its slab is taller:
+// the adds stay in row order g, g + G, ..., so the sum does not depend on U).
 constexpr int RSUM_U = 24;
-template <typename F>
+template <int U = RSUM_U, typename F>
 __device__ __forceinline__ float strided_rowsum(const float* __restrict__ src, int rows, int RL, int j, int g, int G,
                                                 F&& after_issue) {
   // The first batch is peeled out of the loop (at a loop header hipcc waits vmcnt(0) for the
@@ -150,18 +195,18 @@ __device__ __forceinline__ float strided_rowsum(const float* __restrict__ src, i
   // batch is issued behind the kernel's earlier loads instead of a round trip after them.
   float acc = 0.f;
   auto batch = [&](int base, bool first) {
-    float v[RSUM_U];
+    float v[U];
 #pragma unroll
-    for (int u = 0; u < RSUM_U; ++u) {
+    for (int u = 0; u < U; ++u) {
       const int rr = base + u * G;
       v[u] = src[(size_t)min(rr, rows - 1) * RL + j] * (rr < rows ? 1.f : 0.f);
     }
     if (first) after_issue();  // e.g. an atomic whose round trip then overlaps these loads
 #pragma unroll
-    for (int u = 0; u < RSUM_U; ++u) acc += v[u];
+    for (int u = 0; u < U; ++u) acc += v[u];
   };
   batch(g, true);
-  for (int base = g + RSUM_U * G; base < rows; base += RSUM_U * G) batch(base, false);
+  for (int base = g + U * G; base < rows; base += U * G) batch(base, false);
   return acc;
 }
 __device__ __forceinline__ float strided_rowsum(const float* __restrict__ src, int rows, int RL, int j, int g, int G) {
@@ -172,7 +217,8 @@ __device__ __forceinline__ float strided_rowsum(const float* __restrict__ src, i
 // workgroups: the constant, not blockDim.x -- on gfx950 blockDim is a load from the hidden
 // kernel arguments, and the s_waitcnt vmcnt(0) before its use waited for every load the
 // kernel had issued so far (a whole memory round trip ahead of the slab loads, head .s).
-template <int C>
+// U: rows per lane of the slab reduction's one load batch (strided_rowsum).
+template <int C, int U = RSUM_U>
 __device__ __forceinline__ void bn_finalize(const BNParams& bp, float* sc_s, float* beta_s, float* mean_s,
                                             float* istd_s, float* part, int bid) {
   const int tid = threadIdx.x, nthr = NTHR;
@@ -201,7 +247,7 @@ __device__ __forceinline__ void bn_finalize(const BNParams& bp, float* sc_s, flo
       if (xon && tid == 0) tk = xgmi::xsite_ticket(bp.xs, bid);
     };
     if (g < G) {
-      part[tid] = strided_rowsum(bp.fslab, bp.nrows, RL, j, g, G, ticket);
+      part[tid] = strided_rowsum<U>(bp.fslab, bp.nrows, RL, j, g, G, ticket);
     } else {
       ticket();
       part[tid] = 0.f;
@@ -463,25 +509,34 @@ struct BnBwdStage {
 // (lanes along the windows: each load instruction still reads consecutive pairs of
 // one row) and the sink receives the window's 4 pixels as 8-channel vectors: the
 // data-grad kernel writes them as 16-B LDS stores into its [pixel][channel] image.
-template <typename T, int C, int H, int W, int NT_>
+// ROWS (even), r0 (even): as BnBwdStage -- the conv-output rows [r0, r0 + ROWS) of the image,
+// clipped at its end; the sink gets chunk-relative rows.
+template <typename T, int C, int H, int W, int NT_, int ROWS = H>
 struct BnBwdStage8 {
   typedef typename Pair2<T>::type P;
   static_assert(C % 8 == 0 && sizeof(T) == 2, "8-channel staging: 16-bit types, C % 8 == 0");
+  static_assert(ROWS % 2 == 0 && ROWS <= H, "BN-backward staging works on whole 2x2 pooling windows");
   static constexpr int HO = H / 2, WO = W / 2, PP = HO * WO;
-  static constexpr int NO = C / 8, NWIN = NO * PP;
+  static constexpr int CPP = ROWS / 2 * WO;  // windows of one chunk, per channel
+  static constexpr int NO = C / 8, NWIN = NO * CPP;
   static constexpr int IT = (NWIN + NT_ - 1) / NT_;
   P top[IT][8], bot[IT][8];
   T g[IT][8];
   uint8_t ix[IT][8];
+  int ho0 = 0;
 
-  __device__ __forceinline__ void load(const BwdIn<T>& bi, int b) {
+  __device__ __forceinline__ void load(const BwdIn<T>& bi, int b, int r0 = 0) {
+    ho0 = r0 / 2;
     const T* yb = bi.y + (size_t)b * C * H * W;
     const T* dpb = bi.dp + (size_t)b * C * PP;
     const uint8_t* ib = bi.idx + (size_t)b * C * PP;
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int e = min((int)threadIdx.x + i * NT_, NWIN - 1);  // clamped: unconditional loads
-      const int o = e / PP, pix = e % PP, ho = pix / WO, wo = pix % WO;
+      const int o = e / CPP, pl = e % CPP, wo = pl % WO;
+      int ho = pl / WO;
+      if constexpr (ROWS < H) ho = min(ho0 + ho, HO - 1);  // clamped too (emit() skips the row)
+      const int pix = ho * WO + wo;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int c = 8 * o + j;
@@ -494,15 +549,15 @@ struct BnBwdStage8 {
     }
   }
 
-  // sink(h, w, c0, q00, q01, q10, q11): the 4 pixels of window (h, w) (top-left),
-  // channels c0 .. c0+7, each packed as uint4
+  // sink(h, w, c0, q00, q01, q10, q11): the 4 pixels of window (h, w) (top-left, h relative
+  // to r0), channels c0 .. c0+7, each packed as uint4
   template <typename Sink>
   __device__ __forceinline__ void emit(const float* coef, Sink&& sink) {
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
       const int e = (int)threadIdx.x + i * NT_;
-      if (e < NWIN) {
-        const int o = e / PP, pix = e % PP, ho = pix / WO, wo = pix % WO;
+      const int o = e / CPP, pl = e % CPP, ho = pl / WO, wo = pl % WO;
+      if (e < NWIN && (ROWS == H || ho0 + ho < HO)) {
         unsigned q[4][4];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -631,8 +686,14 @@ __host__ __device__ constexpr size_t conv5x5_dyn_bytes() {
 }
 extern __shared__ __attribute__((aligned(16))) unsigned char dpa_dyn_lds[];
 
+// WR: row-window staging (PRO 1 / 2).  A workgroup reads only the input rows of its own output
+// pixels plus two halo rows each side; with WR < H it stages just those (clipped to the image,
+// PRO 2: rounded out to whole 2x2 windows) instead of the whole image, and zeroes just the
+// halo it reads.  WR is the compile-time bound on that row count (conv5x5_win_rows of the
+// launch's nsplit: the launcher checks it); the per-lane trip counts of the staging pass and
+// its register arrays follow from it.  WR = H: every workgroup stages the whole image.
 template <typename T, int CIN, int COUT, int H, int W, int MODE, int PRO = 0, int EPI = 0, int WPK = 0,
-          bool DYN = false>
+          bool DYN = false, int WR = H>
 __device__ __forceinline__ void
 conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
              T* __restrict__ y, float* __restrict__ fslab, float* __restrict__ fstats,
@@ -697,6 +758,27 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   const int sp = bid % nsplit;
   const T* xb = x + (size_t)b * CIN * HW;
   const int mt0 = (MT * sp) / nsplit, mt1 = (MT * (sp + 1)) / nsplit;
+  // this workgroup's output pixels [p_lo, p_hi); the input rows [r_lo, r_lo + SR) it stages (the
+  // rows it needs; past them up to the bound SR, clipped at the image's end) and the padded
+  // LDS rows [z_lo, z_lo + z_n) its MFMA loop reads (wave-uniform)
+  constexpr bool WIN = WR < H;
+  static_assert(!WIN || PRO == 1 || PRO == 2, "row windows: the BN prologues' staging passes");
+  static_assert(WR >= 1 && (PRO != 2 || WR % 2 == 0 || !WIN), "PRO 2 stages whole 2x2 windows");
+  constexpr int SR = WIN ? WR : H;
+  const int p_lo = mt0 * 16, p_hi = min(mt1 * 16, HW);
+  int r_lo = 0, r_n = H, z_lo = 0, z_n = HP;
+  if constexpr (WIN) {
+    const int oh_lo = p_lo / W, oh_hi = (p_hi - 1) / W;
+    r_lo = max(oh_lo - 2, 0);
+    int r_hi = min(oh_hi + 2, H - 1);
+    if constexpr (PRO == 2) {
+      r_lo &= ~1;
+      r_hi |= 1;
+    }
+    r_n = r_hi - r_lo + 1;  // <= WR (host-checked)
+    z_lo = oh_lo;
+    z_n = oh_hi + 5 - oh_lo;
+  }
   // epilogue operands of this lane's channels (co = nt*16 + lane%16), loaded up front
   float pre_bias[NT], pre_shift[NT];
 #pragma unroll
@@ -758,11 +840,20 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   if constexpr ((CIN * sizeof(T)) % 16 == 0) {
     constexpr int G = CIN * (int)sizeof(T) / 16;  // 16-B groups per pixel
     uint4* img4 = reinterpret_cast<uint4*>(img);
-    for (int e = tid; e < HP * WPD * G; e += NTHR) {
-      const int px = e / G, hp = px / WPD, wp = px % WPD;
-      if (hp < 2 || hp >= H + 2 || wp < 2 || wp >= W + 2) img4[e] = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (WIN) {  // the halo pixels of the padded rows this workgroup reads
+      uint4* row4 = img4 + z_lo * WPD * G;
+      for (int e = tid; e < z_n * WPD * G; e += NTHR) {
+        const int px = e / G, hp = z_lo + px / WPD, wp = px % WPD;
+        if (hp < 2 || hp >= H + 2 || wp < 2 || wp >= W + 2) row4[e] = make_uint4(0u, 0u, 0u, 0u);
+      }
+    } else {
+      for (int e = tid; e < HP * WPD * G; e += NTHR) {
+        const int px = e / G, hp = px / WPD, wp = px % WPD;
+        if (hp < 2 || hp >= H + 2 || wp < 2 || wp >= W + 2) img4[e] = make_uint4(0u, 0u, 0u, 0u);
+      }
     }
   } else {
+    static_assert(!WIN, "row windows: whole 16-B channel groups per pixel");
     for (int e = tid; e < HP * WPD * CIN; e += NTHR) {
       const int hp = e / (WPD * CIN), rem = e % (WPD * CIN);
       const int wp = rem / CIN;
@@ -816,8 +907,8 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   // -0.4 us; the same deferral of conv1's gather stores measured no gain,
   // profiles/r4p_deferred_stores_ab.txt)
   constexpr int DQ = PRO != 1 ? 1
-                     : (CIN % 8 == 0 && sizeof(T) == 2) ? 8 * ((CIN / 8 * HW + NTHR - 1) / NTHR)
-                                                          : (CIN * HW + NTHR - 1) / NTHR;
+                     : (CIN % 8 == 0 && sizeof(T) == 2) ? 8 * ((CIN / 8 * SR * W + NTHR - 1) / NTHR)
+                                                          : (CIN * SR * W + NTHR - 1) / NTHR;
   int dq_e[DQ];  // pooled-output element of entry d, -1: none
   T dq_p[DQ], dq_x[DQ];
   uint8_t dq_i[DQ];
@@ -873,28 +964,39 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
     __shared__ float sc_s[CIN], beta_s[CIN], mean_s[CIN], istd_s[CIN];
     __shared__ float part[NTHR];
     typedef typename Pair2<T>::type P;
-    constexpr int NPO = CIN * HW;  // pooled outputs of one image = this conv's input
+    // the staged pooled pixels (= this conv's input) are the rows [r_lo, r_lo + r_n) of every
+    // channel; RP: their compile-time bound per channel (the whole image without a window)
+    constexpr int RP = SR * W;
     const T* yb = pin.y + (size_t)b * CIN * 4 * HW;
+    // The pooled map / index / xhat outputs (for the backward) are written by all nsplit
+    // workgroups of the image: each the pooled pixels of its own output pixel range
+    // [p_lo, p_hi), every channel.  That range lies inside its window and the ranges
+    // partition the image, so every element is written exactly once for any nsplit.
     const bool wr = pin.p_out != nullptr;
-    const int e_lo = NPO * sp / nsplit, e_hi = NPO * (sp + 1) / nsplit;
     if constexpr (CIN % 8 == 0 && sizeof(T) == 2) {
       // a lane owns 8 channels of one pooled pixel (lanes along the pixels: every load
       // instruction reads consecutive pairs of one row): ONE 16-B LDS write of the 8
       // pooled values instead of eight 2-B writes to the same bank group
-      constexpr int NO = CIN / 8, NPI = NO * HW, IT8 = (NPI + NTHR - 1) / NTHR;
+      constexpr int NO = CIN / 8, NPI = NO * RP, IT8 = (NPI + NTHR - 1) / NTHR;
       P top[IT8][8], bot[IT8][8];
+      auto ld8 = [&](int i, int o, int ho, int wo) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const P* src = reinterpret_cast<const P*>(yb + ((size_t)(8 * o + j) * 2 * H + 2 * ho) * 2 * W + 2 * wo);
+          top[i][j] = src[0];
+          bot[i][j] = src[W];  // next input row (2W elements = W pairs)
+        }
+      };
 #pragma unroll
       for (int i = 0; i < IT8; ++i) {  // issued before the statistics reduction: the latencies overlap
         const int e8 = tid + i * NTHR;
-        if (e8 < NPI) {
-          const int o = e8 / HW, pix = e8 % HW, ho = pix / W, wo = pix % W;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const P* src =
-                reinterpret_cast<const P*>(yb + ((size_t)(8 * o + j) * 2 * H + 2 * ho) * 2 * W + 2 * wo);
-            top[i][j] = src[0];
-            bot[i][j] = src[W];  // next input row (2W elements = W pairs)
-          }
+        if constexpr (WIN) {
+          // unconditional (clamped item and row, skipped by the pass below): guarded loads
+          // are branched around and waited for group by group (BnBwdStage::load)
+          const int ec = min(e8, NPI - 1);
+          ld8(i, ec / RP, min(r_lo + (ec % RP) / W, H - 1), ec % W);
+        } else if (e8 < NPI) {
+          ld8(i, e8 / RP, (e8 % RP) / W, e8 % W);
         }
       }
       load_wpk();
@@ -903,8 +1005,10 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
 #pragma unroll
       for (int i = 0; i < IT8; ++i) {
         const int e8 = tid + i * NTHR;
-        if (e8 < NPI) {
-          const int o = e8 / HW, pix = e8 % HW, ho = pix / W, wo = pix % W;
+        const int o = e8 / RP, hl = (e8 % RP) / W, ho = r_lo + hl, wo = e8 % W;
+        if (e8 < NPI && (!WIN || hl < r_n)) {
+          const int pix = ho * W + wo;
+          const bool own = wr && pix >= p_lo && pix < p_hi;
           unsigned pk[4];  // the 8 pooled values packed in registers (no local array in memory)
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
@@ -917,7 +1021,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
             if (j & 1) pk[j >> 1] |= bits << 16; else pk[j >> 1] = bits;
             const int e = ci * HW + pix;  // (ci, pix) index of the pooled outputs
             const int d = i * 8 + j;
-            dq_e[d] = wr && e >= e_lo && e < e_hi ? e : -1;
+            dq_e[d] = own ? e : -1;
             dq_p[d] = pvj;
             dq_i[d] = (uint8_t)(bi | (best > 0.f ? IDX_RELU : 0));
             dq_x[d] = Cvt<T>::from_f(xh);
@@ -927,34 +1031,38 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
         }
       }
     } else {
-      constexpr int IT = (NPO + NTHR - 1) / NTHR;
+      constexpr int NPS = CIN * RP, IT = (NPS + NTHR - 1) / NTHR;  // a lane owns one pooled pixel of one channel
       P top[IT], bot[IT];
+      auto ld1 = [&](int i, int ci, int ho, int wo) {
+        const P* src = reinterpret_cast<const P*>(yb + ((size_t)ci * 2 * H + 2 * ho) * 2 * W + 2 * wo);
+        top[i] = src[0];
+        bot[i] = src[W];  // next input row (2W elements = W pairs)
+      };
 #pragma unroll
       for (int i = 0; i < IT; ++i) {  // issued before the statistics reduction: the latencies overlap
         const int e = tid + i * NTHR;
-        if (e < NPO) {
-          const int ci = e / HW, pix = e % HW, ho = pix / W, wo = pix % W;
-          const P* src = reinterpret_cast<const P*>(yb + ((size_t)ci * 2 * H + 2 * ho) * 2 * W + 2 * wo);
-          top[i] = src[0];
-          bot[i] = src[W];  // next input row (2W elements = W pairs)
+        if constexpr (WIN) {  // unconditional, clamped (see the 8-channel branch)
+          const int ec = min(e, NPS - 1);
+          ld1(i, ec / RP, min(r_lo + (ec % RP) / W, H - 1), ec % W);
+        } else if (e < NPS) {
+          ld1(i, e / RP, (e % RP) / W, e % W);
         }
       }
       load_wpk();
       bn_finalize<CIN>(pin.bn, sc_s, beta_s, mean_s, istd_s, part, bid);
       DPA_STAMP(3);
-      // the pooled map / index / xhat outputs (for the backward) are written by all
-      // nsplit workgroups of the image, each its share (was: split 0 alone)
 #pragma unroll
       for (int i = 0; i < IT; ++i) {
         const int e = tid + i * NTHR;
-        if (e < NPO) {
-          const int ci = e / HW, pix = e % HW, ho = pix / W, wo = pix % W;
+        const int ci = e / RP, hl = (e % RP) / W, ho = r_lo + hl, wo = e % W;
+        if (e < NPS && (!WIN || hl < r_n)) {
+          const int pix = ho * W + wo;
           float best, xh;
           int bi;
           bn_relu_max4x<T>(top[i], bot[i], sc_s[ci], beta_s[ci], mean_s[ci], istd_s[ci], best, bi, xh);
           const T pv = Cvt<T>::from_f(best);
           img[imo((ho + 2) * WPD + (wo + 2), ci)] = pv;
-          dq_e[i] = wr && e >= e_lo && e < e_hi ? e : -1;
+          dq_e[i] = wr && pix >= p_lo && pix < p_hi ? ci * HW + pix : -1;
           dq_p[i] = pv;
           dq_i[i] = (uint8_t)(bi | (best > 0.f ? IDX_RELU : 0));
           dq_x[i] = Cvt<T>::from_f(xh);
@@ -964,33 +1072,39 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   } else {
     __shared__ float coef[5 * CIN], sums[2 * CIN];
     __shared__ float part[NTHR];
+    // the stages produce the windows of rows [r_lo, r_lo + SR) (h: relative to r_lo); this
+    // workgroup's are the first r_n (even) of them
     if constexpr (CIN % 8 == 0 && sizeof(T) == 2) {
-      BnBwdStage8<T, CIN, H, W, NTHR> st;
-      st.load(bin, b);
+      BnBwdStage8<T, CIN, H, W, NTHR, SR> st;
+      st.load(bin, b, r_lo);
       DPA_STAMP(8);
       load_wpk();
       bn_bwd_coef<CIN, T>(bin, coef, part, sums, bid);
       load_epi();
       DPA_STAMP(3);
       st.emit(coef, [&](int h, int ww, int c0, uint4 q00, uint4 q01, uint4 q10, uint4 q11) {
-        *reinterpret_cast<uint4*>(&img[imo((h + 2) * WPD + (ww + 2), c0)]) = q00;
-        *reinterpret_cast<uint4*>(&img[imo((h + 2) * WPD + (ww + 3), c0)]) = q01;
-        *reinterpret_cast<uint4*>(&img[imo((h + 3) * WPD + (ww + 2), c0)]) = q10;
-        *reinterpret_cast<uint4*>(&img[imo((h + 3) * WPD + (ww + 3), c0)]) = q11;
+        if (WIN && h >= r_n) return;
+        const int hp = r_lo + h + 2;
+        *reinterpret_cast<uint4*>(&img[imo(hp * WPD + (ww + 2), c0)]) = q00;
+        *reinterpret_cast<uint4*>(&img[imo(hp * WPD + (ww + 3), c0)]) = q01;
+        *reinterpret_cast<uint4*>(&img[imo((hp + 1) * WPD + (ww + 2), c0)]) = q10;
+        *reinterpret_cast<uint4*>(&img[imo((hp + 1) * WPD + (ww + 3), c0)]) = q11;
       });
     } else {
-      BnBwdStage<T, CIN, H, W, NTHR> st;
-      st.load(bin, b);
+      BnBwdStage<T, CIN, H, W, NTHR, SR> st;
+      st.load(bin, b, r_lo);
       DPA_STAMP(8);
       load_wpk();
       bn_bwd_coef<CIN, T>(bin, coef, part, sums, bid);
       load_epi();
       DPA_STAMP(3);
       st.emit(coef, [&](int c, int h, int ww, T v00, T v01, T v10, T v11) {
-        img[imo((h + 2) * WPD + (ww + 2), c)] = v00;
-        img[imo((h + 2) * WPD + (ww + 3), c)] = v01;
-        img[imo((h + 3) * WPD + (ww + 2), c)] = v10;
-        img[imo((h + 3) * WPD + (ww + 3), c)] = v11;
+        if (WIN && h >= r_n) return;
+        const int hp = r_lo + h + 2;
+        img[imo(hp * WPD + (ww + 2), c)] = v00;
+        img[imo(hp * WPD + (ww + 3), c)] = v01;
+        img[imo((hp + 1) * WPD + (ww + 2), c)] = v10;
+        img[imo((hp + 1) * WPD + (ww + 3), c)] = v11;
       });
     }
     store_epi();
@@ -1107,15 +1221,15 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   DPA_STAMP(7);
 }
 
-template <typename T, int CIN, int COUT, int H, int W, int MODE, int PRO = 0, int EPI = 0, int WPK = 0>
+template <typename T, int CIN, int COUT, int H, int W, int MODE, int PRO = 0, int EPI = 0, int WPK = 0, int WR = H>
 __global__ void __launch_bounds__(NTHR)
 conv5x5_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                T* __restrict__ y, float* __restrict__ fslab, float* __restrict__ fstats,
                const float* __restrict__ shift, int nsplit, PoolIn<T> pin = PoolIn<T>{},
                BwdIn<T> bin = BwdIn<T>{}, BwdEpi<T> epi = BwdEpi<T>{}, const T* __restrict__ wpk = nullptr,
                WPack<T> pk = WPack<T>{}, GatherIn gin = GatherIn{}) {
-  conv5x5_body<T, CIN, COUT, H, W, MODE, PRO, EPI, WPK>(x, w, bias, y, fslab, fstats, shift, nsplit, pin, bin, epi,
-                                                        wpk, pk, (int)blockIdx.x, gin);
+  conv5x5_body<T, CIN, COUT, H, W, MODE, PRO, EPI, WPK, false, WR>(x, w, bias, y, fslab, fstats, shift, nsplit, pin,
+                                                                   bin, epi, wpk, pk, (int)blockIdx.x, gin);
 }
 
 // ---------------------------------------------------------------------------

@@ -256,14 +256,29 @@ static BwdIn<T> bwd_in(at::Tensor dp, at::Tensor idx, at::Tensor y, at::Tensor f
 typedef std::shared_ptr<xgmi::XgmiComm> XcPtr;
 static xgmi::XSite site_of(const XcPtr& xc, int s) { return xc ? xc->site(s) : xgmi::XSite{}; }
 
-// Workgroups per image of the conv2 forward.  bf16 / fp16: cb::SH<1>::SPLIT (2); fp32, whose
-// 16x16x4 MFMA chain per output tile is 4x as long, runs 4 shorter workgroups per image: fp32
-// step 0.0640 -> 0.0617 ms, while bf16 at 4 is 0.6 us slower (profiles/r6m_split_ab.txt).
+// Workgroups per image of the conv2 forward: cb::kFwd2SplitT<T> (convblock_impl.h; the knobs
+// DPA_FWD2_SPLIT / DPA_FWD2_SPLIT_F32).  fp32, whose 16x16x4 MFMA chain per output tile is 4x
+// as long, runs 4 workgroups per image (fp32 step 0.0640 -> 0.0617 ms, profiles/r6m_split_ab.txt).
 // The consumers take the slab's row count from its size (nrows).
-#ifndef DPA_FWD2_SPLIT_F32
-#define DPA_FWD2_SPLIT_F32 4
-#endif
-int64_t fwd2_split(bool fp32) { return fp32 ? DPA_FWD2_SPLIT_F32 : cb::SH<1>::SPLIT; }
+int64_t fwd2_split(bool fp32) { return fp32 ? cb::kFwd2SplitT<float> : cb::kFwd2SplitT<__half>; }
+
+// Row windows (cb::conv5x5_body WR): each workgroup of the fused conv2 kernels stages the
+// input rows its own output pixels read, not the whole image.  The kernels' compile-time
+// row bound follows from the split count; conv2_row_window re-derives what the launch's
+// nsplit needs and refuses a launch whose splits would not fit the bound.
+template <int NSPLIT, bool EVEN>
+constexpr int conv2_wr() {
+  constexpr int need = cb::conv5x5_win_rows(14, 14, NSPLIT, EVEN);
+  static_assert(need > 0, "conv2: more workgroups per image than 16-pixel tiles");
+  return cb::kConv2RowWindow && need < 14 ? need : 14;
+}
+static void conv2_row_window(int wr, int nsplit, bool even, const char* what) {
+  const int need = cb::conv5x5_win_rows(14, 14, nsplit, even);
+  TORCH_CHECK(need > 0 && (wr >= 14 || need <= wr), what, ": a split in ", nsplit, " stages up to ", need,
+              " rows, the kernel's window holds ", wr);
+}
+template <typename T>
+constexpr int kFwd2WR = conv2_wr<cb::kFwd2SplitT<T>, false>();
 
 // [BN1 -> ReLU -> pool1] -> conv2 (+ BN2 partial sums when training).
 void conv2_fwd(at::Tensor y1, c10::optional<at::Tensor> fslab1, at::Tensor fstats1, at::Tensor g1, at::Tensor b1,
@@ -295,13 +310,15 @@ void conv2_fwd(at::Tensor y1, c10::optional<at::Tensor> fslab1, at::Tensor fstat
     PoolIn<T> pin{dptr<T>(y1), bp, p1_out.has_value() ? dptr<T>(*p1_out) : nullptr,
                   idx1_out.has_value() ? idx1_out->data_ptr<uint8_t>() : nullptr,
                   xh1_out.has_value() ? dptr<T>(*xh1_out) : nullptr};
+    constexpr int WR = kFwd2WR<T>;
+    conv2_row_window(WR, ns, false, "conv2_fwd");
     if (train)
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 16, 32, 14, 14, 0, 1, 0, 1>), dim3(B * ns), dim3(cb::NTHR), 0,
+      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 16, 32, 14, 14, 0, 1, 0, 1, WR>), dim3(B * ns), dim3(cb::NTHR), 0,
                          stream, nullptr, nullptr, bias2.data_ptr<float>(), dptr<T>(y2), fslab2->data_ptr<float>(),
                          fstats2.data_ptr<float>(), rm2.data_ptr<float>(), ns, pin, BwdIn<T>{}, BwdEpi<T>{},
                          dptr<T>(wpk), cb::WPack<T>{});
     else
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 16, 32, 14, 14, 1, 1, 0, 1>), dim3(B * ns), dim3(cb::NTHR), 0,
+      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 16, 32, 14, 14, 1, 1, 0, 1, WR>), dim3(B * ns), dim3(cb::NTHR), 0,
                          stream, nullptr, nullptr, bias2.data_ptr<float>(), dptr<T>(y2), nullptr, nullptr, nullptr,
                          ns, pin, BwdIn<T>{}, BwdEpi<T>{}, dptr<T>(wpk), cb::WPack<T>{});
   });
@@ -454,10 +471,19 @@ void conv1_fwd_pack_gather(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tenso
   DPA_CHECK_LAUNCH();
 }
 
-// Workgroups per image of the conv2 data gradient: 2 for bf16 / fp16 (4: +2.5 us,
-// profiles/r6m_split_ab.txt, r6ax_*), 4 for fp32, whose 16x16x4 MFMA chains are 4x as long
-// (profiles/r6bf_fp32_dgrad_split_ab.txt).  Compile-time per dtype: the kernels take it as a
-// constant (kDgradSplitT<T>), the host sizes follow from the tensor dtype (dgrad_split).
+// Workgroups per image of the conv2 data gradient: 2 for bf16 / fp16, 4 for fp32, whose
+// 16x16x4 MFMA chains are 4x as long (profiles/r6bf_fp32_dgrad_split_ab.txt).
+// bf16 / fp16 at 4 measure FASTER on one GPU once the splits stage row windows (a quarter runs
+// one m-tile per wave: MFMA loop 2.0 -> 1.2 us; bf16 step 0.0409 -> 0.0402 ms with the forward
+// at 4, profiles/conv2_rowwin_ab.txt; staging the whole image it was +2.5 us, r6m_split_ab.txt),
+// but the merged backward launch then has 128 + 128 + 7 = 263 workgroups at batch 32, more
+// than sites_resident() accepts at 2 per CU (co_resident keeps one in reserve: 256), so SyncBN
+// would leave the in-kernel exchange for an all-reduce per sum, and two ranks sharing a card
+// would not fit it together.  It stays at 2 until that launch is smaller.
+// The staging pass is one iteration per lane at 2 and at 4 (5 pooled rows x 7 x 4 channel
+// groups = 140 windows of 256 lanes): the window shortens no chain there, it removes loads.
+// Compile-time per dtype: the kernels take it as a constant (kDgradSplitT<T>), the host sizes
+// follow from the tensor dtype (dgrad_split).
 #ifndef DPA_DGRAD2_SPLIT
 #define DPA_DGRAD2_SPLIT 2
 #endif
@@ -467,6 +493,16 @@ void conv1_fwd_pack_gather(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tenso
 template <typename T>
 constexpr int kDgradSplitT = std::is_same<T, float>::value ? DPA_DGRAD2_SPLIT_F32 : DPA_DGRAD2_SPLIT;
 static int dgrad_split(bool fp32) { return fp32 ? DPA_DGRAD2_SPLIT_F32 : DPA_DGRAD2_SPLIT; }
+template <typename T>
+constexpr int kDgrad2WR = conv2_wr<kDgradSplitT<T>, true>();  // whole 2x2 windows: even rows
+// the data-gradient role's kernel body, one spelling for every launch that hosts it
+template <typename T, bool DYN>
+__device__ __forceinline__ void conv2_dgrad_role(const T* __restrict__ wpk_d, T* __restrict__ dp1,
+                                                 const BwdIn<T>& bi_d, const BwdEpi<T>& ep, int bid) {
+  cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1, DYN, kDgrad2WR<T>>(nullptr, nullptr, nullptr, dp1, nullptr, nullptr,
+                                                                     nullptr, kDgradSplitT<T>, PoolIn<T>{}, bi_d, ep,
+                                                                     wpk_d, cb::WPack<T>{}, bid);
+}
 int64_t dgrad2_rows(int64_t B, bool fp32) { return B * dgrad_split(fp32); }
 
 // [pool2/ReLU2/BN2 backward] -> conv2 data grad -> dp1 (+ BN1 partial sums rows).
@@ -484,11 +520,12 @@ void conv2_dgrad(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx
   with_t(dt_of(y2), [&](auto tag) {
     typedef decltype(tag) T;
     constexpr int ds = kDgradSplitT<T>;
+    conv2_row_window(kDgrad2WR<T>, ds, true, "conv2_dgrad");
     BwdIn<T> bi = bwd_in<T>(dp2, idx2, y2, fstats2, gsum2, c10::nullopt, g2, eps2, 32, c10::nullopt, c10::nullopt);
     bi.xs = site_of(xc, xgmi::kSiteBwd2Dgrad);
     xgmi::set_site_grid(bi.xs, B * ds, "conv2_dgrad");
     BwdEpi<T> ep{idx1.data_ptr<uint8_t>(), dptr<T>(xh1), bslab1.data_ptr<float>()};
-    hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1>), dim3(B * ds), dim3(cb::NTHR),
+    hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<T>>), dim3(B * ds), dim3(cb::NTHR),
                        0, cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr, nullptr, nullptr,
                        ds, PoolIn<T>{}, bi, ep, dptr<T>(wpk_d), cb::WPack<T>{});
   });
@@ -623,8 +660,7 @@ conv2_bwd_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d
                  const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int ndg, int nwg, FcW<T> fw) {
   const int bid = (int)blockIdx.x;
   if (bid < ndg)
-    cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1>(nullptr, nullptr, nullptr, dp1, nullptr, nullptr, nullptr,
-                                                    kDgradSplitT<T>, PoolIn<T>{}, bi_d, ep, wpk_d, cb::WPack<T>{}, bid);
+    conv2_dgrad_role<T, false>(wpk_d, dp1, bi_d, ep, bid);
   else if (bid < ndg + nwg)
     conv2_wgrad_role<T, false>(p1, wslab2, bi_w, bid - ndg);
   else
@@ -644,9 +680,7 @@ conv2_bwd_dyn_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> 
                      FcW<T> fw) {
   const int bid = (int)blockIdx.x;
   if (bid < ndg)
-    cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1, true>(nullptr, nullptr, nullptr, dp1, nullptr, nullptr, nullptr,
-                                                          kDgradSplitT<T>, PoolIn<T>{}, bi_d, ep, wpk_d,
-                                                          cb::WPack<T>{}, bid);
+    conv2_dgrad_role<T, true>(wpk_d, dp1, bi_d, ep, bid);
   else if (bid < ndg + nwg)
     conv2_wgrad_role<T, true>(p1, wslab2, bi_w, bid - ndg);
   else
@@ -773,6 +807,7 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
   if (B == 0) return;
   with_t(dt_of(y2), [&](auto tag) {
     typedef decltype(tag) T;
+    conv2_row_window(kDgrad2WR<T>, kDgradSplitT<T>, true, "conv2_bwd data gradient");
     BwdIn<T> bd = bwd_in<T>(dp2, idx2, y2, fstats2, gsum2, lsum2, g2, eps2, 32, dg2, dbe2);
     BwdIn<T> bw = bd;
     bw.dgamma = bw.dbeta = nullptr;  // one writer: the data-gradient role's workgroup 0
@@ -799,7 +834,7 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
       // (the fc weight gradient: extra workgroups of the weight-gradient launch; its site's
       // tickets are the nwg conv workgroups', set above)
       bd.xs.nblk = 0;  // the data-gradient launch is its site's whole grid (ndg: checked above)
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1>), dim3(ndg), dim3(cb::NTHR), 0,
+      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<T>>), dim3(ndg), dim3(cb::NTHR), 0,
                          cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr, nullptr, nullptr,
                          kDgradSplitT<T>, PoolIn<T>{}, bd, ep, dptr<T>(wpk_d), cb::WPack<T>{});
       hipLaunchKernelGGL(conv2_wgrad_fc_kernel<T>, dim3(nwg + nfc), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(p1),
@@ -1212,11 +1247,11 @@ bool sites_resident(int64_t B, at::ScalarType st) {
   auto chk = [&](const void* k, int64_t grid) { ok = ok && co_resident(k, (int)grid, cb::NTHR, 0); };
   with_t(dt_of(at::empty({0}, at::TensorOptions().dtype(st))), [&](auto tag) {
     typedef decltype(tag) T;
-    chk(reinterpret_cast<const void*>(&cb::conv5x5_kernel<T, 16, 32, 14, 14, 0, 1, 0, 1>),
+    chk(reinterpret_cast<const void*>(&cb::conv5x5_kernel<T, 16, 32, 14, 14, 0, 1, 0, 1, kFwd2WR<T>>),
         B * fwd2_split(std::is_same<T, float>::value));
     ok = ok && co_resident(reinterpret_cast<const void*>(&head_fwd_kernel<T, 32, 14, 14, 16>), (int)B, HF, 0) &&
          co_resident(reinterpret_cast<const void*>(&head_fwd_kernel<T, 32, 14, 14, 64>), (int)B, HF, 0);
-    chk(reinterpret_cast<const void*>(&cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1>), B * kDgradSplitT<T>);
+    chk(reinterpret_cast<const void*>(&cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<T>>), B * kDgradSplitT<T>);
     if constexpr (!std::is_same<T, float>::value) {
       if (lp_dyn_bwd())
         ok = ok && co_resident(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<T>),

@@ -127,7 +127,11 @@ head_row_kernel(const T* __restrict__ y, BNParams bn, const float* __restrict__ 
   const int64_t tgt = hr.target[b];
   const float scv = hr.scale[0];
   DPA_STAMP(1);
-  cb::bn_finalize<C>(bn, sc_s, beta_s, mean_s, istd_s, part_s, b);  // ends with a barrier
+  // the BN2 slab has batch x (conv2 forward workgroups per image) rows, summed by G = NTHR / 65 = 3
+  // lane groups: the one load batch holds batch 32 at either split count (64 | 128 rows).
+  // Not the 1024-lane form: its 128-VGPR budget has no room for the taller batch (it spilt).
+  constexpr int RU = NT == 256 && cb::kFwd2SplitT<T> > 2 ? (32 * cb::kFwd2SplitT<T> + 2) / 3 : cb::RSUM_U;
+  cb::bn_finalize<C, RU>(bn, sc_s, beta_s, mean_s, istd_s, part_s, b);  // ends with a barrier
   DPA_STAMP(2);
   if (hr.chk != nullptr && b == 0 && tid == 0) {  // the step's gradient-check words (GradChk)
     hr.chk[0] = 0;

@@ -57,6 +57,8 @@ def summarize(name, rows):
 
 
 def wrap(mod, name, roles):
+    if not hasattr(mod, "clear_stamps"):  # a translation unit built without -DDPA_TIMING
+        return
     f = getattr(mod, name)
 
     def g(*a):
@@ -72,10 +74,12 @@ def wrap(mod, name, roles):
 
 
 B = 32
+NDG = int(C.convnet.dgrad2_rows(B, False))      # data-gradient workgroups (bf16 split count x B)
+NFW = int(C.convnet.fwd2_split(False)) * B      # conv2 forward workgroups
 wrap(C.convnet_head, "head_step", lambda a: [("head_step", slice(0, 32))])
-wrap(C.convnet, "conv2_bwd", lambda a: [("conv2_bwd/dgrad", slice(0, 2 * B)),
-                                         ("conv2_bwd/wgrad", slice(2 * B, 2 * B + 4 * B))])
-wrap(C.convnet, "conv2_fwd", lambda a: [("conv2_fwd", slice(0, 2 * B))])
+wrap(C.convnet, "conv2_bwd", lambda a: [("conv2_bwd/dgrad", slice(0, NDG)),
+                                         ("conv2_bwd/wgrad", slice(NDG, NDG + 4 * B))])
+wrap(C.convnet, "conv2_fwd", lambda a: [("conv2_fwd", slice(0, NFW))])
 wrap(C.convnet, "wgrad1_reduce", lambda a: [("wgrad1_reduce/wgrad", slice(0, 7 * B))])
 wrap(C.convnet, "conv1_wgrad_slab2", lambda a: [("wgrad1_slab2/wgrad", slice(0, 7 * B)),
                                                  ("wgrad1_slab2/sums", slice(7 * B, 512))])
