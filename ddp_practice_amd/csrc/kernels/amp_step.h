@@ -1,7 +1,5 @@
 // The fused AMP optimizer step (GradScaler.step + SGD + GradScaler.update in ONE
-// launch), shared by csrc/kernels/optim.hip (amp_sgd_fused: any small parameter set)
-// and csrc/kernels/convnet_fused.hip (convnet_amp_step: the ConvNet's step with the
-// conv1 weight gradient computed by producer workgroups of the same launch).
+// launch) of csrc/kernels/optim.hip (amp_sgd_fused: any small parameter set).
 // Reference call sites: /root/reference/ddp_main.py:91-93 (scaler.scale/step/update),
 // origin_main.py:87 (SGD lr=1e-4); torch semantics: torch/amp/grad_scaler.py:235-286,
 // 348-357, 500-537 and torch/optim/sgd.py:471.
@@ -59,78 +57,24 @@ constexpr int64_t FUSED_MAX = (int64_t)FUSED_MAX_BLOCKS * FUSED_BLOCK_GRAN * 4;
 // values in rank order and divides by W before the inf check -- the reducer launched
 // no collective for these buckets.  U = 1 granule per lane then.
 //
-// Slab sources (optional, up to kMaxSlabs): a gradient region [out, out + n) that is
-// still the per-workgroup partial rows of its producer (slab [rows][n]: e.g. the
-// ConvNet's weight-gradient slabs).  nblk extra workgroups per source, appended after
-// the granule workgroups, own it -- they sum its columns (`cols` columns x 256/cols row
-// groups each), check them, load the matching params / buffers, take part in the
-// gradient exchange (XG: one granule per element, at the element's position in the
-// flat granule space), arrive at the grid barrier like the others and then apply the
-// same update per element (unscaled gradient written to `out`).  The granule
-// workgroups skip the regions, and the separate column-sum launches disappear.  A
-// source with `wait` is produced IN THIS LAUNCH: its owners first wait (bounded) until
-// the producers' arrival counter reaches wait_n and then read the rows with L2-coherent
-// (sc1) loads; block 0 re-arms the counter after the barrier.
-// Association: a column is summed over rows g, g + G, ... (g < G row groups of 256/G lanes)
-// and the G partials are added in group order -- slab_reduce's (G = 16) and the BN
-// backward-coefficient reduction's (cb::colsum_rows over 2C = 32 columns: G = 8), so a
-// gradient summed here is bitwise the one the separate launches produce (the flush path).
+// Slab source (optional, nblk > 0): a gradient region [out, out + n) that is still the
+// per-workgroup partial rows of its producer, a launch that has finished (slab [rows][n]:
+// the ConvNet's conv1 weight-gradient slab).  nblk extra workgroups, appended after the
+// granule workgroups, own it -- they sum its columns (SLAB_CC columns x SLAB_G row groups
+// each), check them, load the matching params / buffers, take part in the gradient
+// exchange (XG: one granule per element, at the element's position in the flat granule
+// space), arrive at the grid barrier like the others and then apply the same update per
+// element (unscaled gradient written to `out`).  The granule workgroups skip the region,
+// and the separate column-sum launch disappears.
+// Association: a column is summed over rows g, g + G, ... (g < G = 16 row groups of 16
+// lanes, common.h slab_colsum) and the G partials are added in group order -- slab_reduce's,
+// so a gradient summed here is bitwise the one the separate launch produces (the flush path).
 struct SlabSrc {
   const float* slab = nullptr;
   float* out = nullptr;
   int rows = 0, n = 0, nblk = 0;
-  int groups = 16;            // row groups G: 16 (16 columns per chunk) or 8 (32 columns)
-  int chunks = 1;             // column chunks per workgroup: 1 or 4 (G = 16)
-  const int* wait = nullptr;  // in-launch producers' arrival counter (nullptr: rows ready)
-  int wait_n = 0;
 };
-constexpr int kMaxSlabs = 3;
-struct SlabSet {
-  SlabSrc s[kMaxSlabs];
-  int ns = 0;
-  int* rearm = nullptr;  // producer counter zeroed by block 0 after the barrier
-  int blanes = 1;        // grid-barrier arrival words (> 1: kBarStride u64 apart, sync holds
-                         // 1 + 2 * blanes * kBarStride words): arrivals of a few hundred
-                         // workgroups on ONE word serialise (~10 ns each)
-};
-constexpr int kBarStride = 8;  // u64: 64 B
-
-__device__ __forceinline__ float ld_sc1(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// K column chunks of CC = 256/G columns at c0, c0 + CC, ...: this lane's column of each
-// chunk (c0 + j*CC + tid % CC) summed over rows g, g + G, ... in that order, g = tid / CC.
-// Every chunk's first 16 rows per lane are loaded before any add (one round trip for the
-// ConvNet's <= 16 G-row slabs); clamped, masked.  SC1: L2-coherent loads (rows written by
-// other workgroups of this launch).
-template <int G, int K, bool SC1>
-__device__ __forceinline__ void slab_colsum_k(const float* __restrict__ slab, int rows, int n, int c0, float* out) {
-  constexpr int CC = 256 / G;
-  const int g = threadIdx.x / CC, cl = threadIdx.x % CC;
-  float v[K][16];
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const int cc = min(c0 + j * CC + cl, n - 1);
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const float* p = slab + (size_t)min(g + u * G, rows - 1) * n + cc;
-      v[j][u] = SC1 ? ld_sc1(p) : *p;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const int cc = min(c0 + j * CC + cl, n - 1);
-    float a = 0.f;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) a += (g + u * G < rows) ? v[j][u] : 0.f;
-    for (int r = g + 16 * G; r < rows; r += G) {  // slabs taller than 16 G rows
-      const float* p = slab + (size_t)r * n + cc;
-      a += SC1 ? ld_sc1(p) : *p;
-    }
-    out[j] = a;
-  }
-}
+constexpr int SLAB_G = 16, SLAB_CC = FUSED_THR / SLAB_G;  // row groups, columns per workgroup
 
 // bid: this workgroup's index among the launch's AMP workgroups; grid: their count.
 template <int U, bool XG, int THR = FUSED_THR>
@@ -138,8 +82,9 @@ __device__ __forceinline__ void
 amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ tracker, float* __restrict__ found_inf,
              unsigned long long* __restrict__ sync, float lr, float momentum, float dampening, float wd, int nesterov,
              int maximize, float growth, float backoff, int interval, const xgmi::XSite& xg, int* __restrict__ err,
-             long long barrier_ticks, const SlabSet& ss, int grid, int bid, const int* __restrict__ chk = nullptr,
+             long long barrier_ticks, const SlabSrc& S, int grid, int bid, const int* __restrict__ chk = nullptr,
              int nchk = 0) {
+  static_assert(THR == FUSED_THR, "the slab workgroups' lane layout (SLAB_CC columns x SLAB_G row groups)");
   constexpr int BG = THR * U;  // float4 granules per workgroup
   __shared__ int soff[MAXT + 1];
   __shared__ int snum[MAXT];
@@ -147,13 +92,13 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
   __shared__ float* sp1[MAXT];
   __shared__ float* sp2[MAXT];
   __shared__ int s_bad;
-  __shared__ float spart[16 * 65];   // slab workgroups: G row groups x (columns + 1)
+  __shared__ float spart[SLAB_G * (SLAB_CC + 1)];  // slab workgroups: row groups x (columns + 1)
   const int tid = threadIdx.x;
   const int n = L.n;
   // scale == nullptr: the plain (unscaled fp32) SGD step -- no unscale, no non-finite
   // agreement, no grid barrier, no scale update: torch.optim.SGD's semantics, with the
-  // slab sums and the DDP average (XG) still inside this launch.  A workgroup whose slab
-  // producers or peers never arrived (error word set) skips its own update only.
+  // slab sums and the DDP average (XG) still inside this launch.  A workgroup whose
+  // peers never arrived (error word set) skips its own update only.
   const bool amp = scale != nullptr;
   {  // the table: every load issued before any LDS write (clamped index; a guarded load was
      // branched and waited for before the next group's loads were issued)
@@ -206,36 +151,19 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
     if (rem >= 4) { *reinterpret_cast<f32x4*>(p) = v; return; }
     for (int j = 0; j < rem; ++j) p[j] = v[j];
   };
-  auto in_slab = [&](const float* gp) {
-#pragma unroll
-    for (int s = 0; s < kMaxSlabs; ++s)
-      if (s < ss.ns && gp >= ss.s[s].out && gp < ss.s[s].out + ss.s[s].n) return true;
-    return false;
-  };
+  auto in_slab = [&](const float* gp) { return gp >= S.out && gp < S.out + S.n; };  // (no slab: n = 0)
   f32x4 gv[U], pv[U], bv[U];
   int tt[U];  // tensor of each granule (its offset is recomputed after the barrier)
   bool bad = false;
-  int nslab = 0;
-#pragma unroll
-  for (int s = 0; s < kMaxSlabs; ++s) nslab += s < ss.ns ? ss.s[s].nblk : 0;
-  const int nreg = grid - nslab;  // granule workgroups; the rest own the slab regions
-  // slab workgroup lane (< cols): its column's sum, tensor and element, param / buffer
+  const int nreg = grid - S.nblk;  // granule workgroups; the rest own the slab region
+  // slab workgroup lane (< SLAB_CC): its column's sum, tensor and element, param / buffer
   float st_sum = 0.f, st_p = 0.f, st_b = 0.f;
   int st_t = -1, st_e = 0;
-  bool wait_fail = false;  // lane 0 of a slab workgroup whose producers never all arrived
   if (bid >= nreg) {
-    int si = 0, base = nreg;
-#pragma unroll
-    for (int s = 0; s + 1 < kMaxSlabs; ++s)
-      if (si == s && s + 1 < ss.ns && bid >= base + ss.s[s].nblk) {
-        base += ss.s[s].nblk;
-        si = s + 1;
-      }
-    const SlabSrc S = ss.s[si];
-    const int G = S.groups, CC = THR / G, K = S.chunks, cols = CC * K;
-    const int c0 = (bid - base) * cols;
-    const int col = c0 + tid;  // the column this lane owns (tid < cols)
-    if (tid < cols && col < S.n) {  // param / buffer loads in flight with the slab's
+    constexpr int G = SLAB_G, CC = SLAB_CC;
+    const int c0 = (bid - nreg) * CC;
+    const int col = c0 + tid;  // the column this lane owns (tid < CC)
+    if (tid < CC && col < S.n) {  // param / buffer loads in flight with the slab's
       const float* gp = S.out + col;
       for (int i = 0; i < n; ++i)  // the tensor whose gradient holds this column (host-checked: one)
         if (gp >= sp1[i] && gp < sp1[i] + snum[i]) {
@@ -247,40 +175,14 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
         if (momentum != 0.f && !((L.first_bits >> st_t) & 1ull)) st_b = sp2[st_t][st_e];
       }
     }
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    const bool sc1 = S.wait != nullptr;
-    if (sc1) {
-      // rows produced in this launch: wait (bounded) for every producer's arrival
-      if (tid == 0) {
-        const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-        while (__hip_atomic_load(S.wait, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < S.wait_n) {
-          __builtin_amdgcn_s_sleep(1);
-          if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > barrier_ticks) {
-            if (err != nullptr) __hip_atomic_store(err, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            wait_fail = true;  // the rows are incomplete: the step must be skipped
-            break;
-          }
-        }
-      }
-      __syncthreads();
-      DPA_STAMP(10);
-    }
-    if (G == 8)
-      slab_colsum_k<8, 1, false>(S.slab, S.rows, S.n, c0, v);
-    else if (K == 4)
-      slab_colsum_k<16, 4, false>(S.slab, S.rows, S.n, c0, v);
-    else if (sc1)
-      slab_colsum_k<16, 1, true>(S.slab, S.rows, S.n, c0, v);
-    else
-      slab_colsum_k<16, 1, false>(S.slab, S.rows, S.n, c0, v);
     const int g = tid / CC, cl = tid % CC;
-    for (int j = 0; j < K; ++j) spart[g * (cols + 1) + j * CC + cl] = v[j];
+    spart[g * (CC + 1) + cl] = slab_colsum<G>(S.slab, S.rows, S.n, c0 + cl, g);
     __syncthreads();
-    if (tid < cols && col < S.n) {
-      for (int gg = 0; gg < G; ++gg) st_sum += spart[gg * (cols + 1) + tid];
+    if (tid < CC && col < S.n) {
+#pragma unroll
+      for (int gg = 0; gg < G; ++gg) st_sum += spart[gg * (CC + 1) + tid];
       bad = amp && !isfinite(st_sum);
     }
-    bad |= wait_fail;
 #pragma unroll
     for (int k = 0; k < U; ++k) tt[k] = -1;
   } else {
@@ -415,11 +317,9 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
   if (grid == 1 || !amp || pre) {  // uniform: one workgroup, the plain step or pre-checked gradients need no grid barrier
     if (tid == 0) s_bad = block_bad;
   } else if (tid == 0) {
-    // arrival words of this launch's parity: one (blanes == 1) or blanes, kBarStride apart
-    const int nl = ss.blanes, st = nl > 1 ? kBarStride : 1;
-    unsigned long long* words = &sync[1 + (int)(gen & 1) * nl * st];
+    unsigned long long* word = &sync[1 + (int)(gen & 1)];  // this launch's parity
     const unsigned long long Gn = (unsigned long long)grid;
-    __hip_atomic_fetch_add(words + (bid % nl) * st, 1ull | ((unsigned long long)block_bad << 32), __ATOMIC_RELAXED,
+    __hip_atomic_fetch_add(word, 1ull | ((unsigned long long)block_bad << 32), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     // bounded: the host sizes the grid to be co-resident, so every workgroup arrives;
     // should one never do, give up after barrier_ticks, flag it and skip the update.
@@ -427,14 +327,9 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
     const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
     bool timed_out = false, any = false;
     for (;;) {
-      unsigned long long cnt = 0;
-      any = false;
-      for (int l = 0; l < nl; ++l) {
-        const unsigned long long v = __hip_atomic_load(words + l * st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cnt += v & 0xffffffffull;
-        any |= (v >> 32) != 0;
-      }
-      if (cnt >= Gn) break;
+      const unsigned long long v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      any = (v >> 32) != 0;
+      if ((v & 0xffffffffull) >= Gn) break;
       __builtin_amdgcn_s_sleep(1);
       if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > barrier_ticks) {
         timed_out = true;
@@ -444,12 +339,8 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
     }
     s_bad = timed_out || any;
     if (bid == 0) {
-      unsigned long long* other = &sync[1 + (int)((gen + 1) & 1) * nl * st];
-      for (int l = 0; l < nl; ++l)
-        __hip_atomic_store(other + l * st, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&sync[1 + (int)((gen + 1) & 1)], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_fetch_add(&sync[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // every slab owner waiting on the in-launch producers passed its wait before arriving
-      if (ss.rearm != nullptr) __hip_atomic_store(ss.rearm, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   __syncthreads();
@@ -507,7 +398,7 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
 }
 
 // ---------------------------------------------------------------------------
-// Host helpers (amp_sgd_fused, convnet_amp_step)
+// Host helpers (amp_sgd_fused)
 // ---------------------------------------------------------------------------
 // tensor table in float4 granules (every tensor 16-B aligned, momentum needs buffers)
 inline MTList fused_list(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
@@ -541,15 +432,9 @@ inline MTList fused_list(const std::vector<at::Tensor>& params, const std::vecto
   return L;
 }
 
-// one slab source: slab [rows][out.numel()] -> the gradient region `out`, which must start
+// the slab source: slab [rows][out.numel()] -> the gradient region `out`, which must start
 // and end on granule boundaries of the tensors that cover it
-inline void add_slab(SlabSet& ss, const MTList& L, const at::Tensor& slab, const at::Tensor& out, int groups,
-                     int chunks, const int* wait, int wait_n) {
-  TORCH_CHECK(ss.ns < kMaxSlabs, "fused AMP-SGD: at most ", kMaxSlabs, " slab sources");
-  TORCH_CHECK((groups == 16 && (chunks == 1 || chunks == 4)) || (groups == 8 && chunks == 1),
-              "fused AMP-SGD: slab layouts G = 16 x 1 | 4 chunks, G = 8 x 1 chunk");
-  TORCH_CHECK(wait == nullptr || (groups == 16 && chunks == 1), "fused AMP-SGD: an in-launch slab is G = 16 x 1");
-  const int cols = 256 / groups * chunks;
+inline SlabSrc slab_src(const MTList& L, const at::Tensor& slab, const at::Tensor& out) {
   TORCH_CHECK(slab.is_cuda() && slab.is_contiguous() && slab.scalar_type() == at::kFloat && out.is_cuda() &&
                   out.is_contiguous() && out.scalar_type() == at::kFloat, "fused AMP-SGD: f32 slab / out");
   const int64_t ncol = out.numel();
@@ -564,18 +449,13 @@ inline void add_slab(SlabSet& ss, const MTList& L, const at::Tensor& slab, const
     TORCH_CHECK(a >= lo && b <= hi && (L.numel[i] % 4 == 0 || b == hi),
                 "fused AMP-SGD: every gradient overlapping slab_out must lie inside it, in whole granules");
   }
-  for (int s = 0; s < ss.ns; ++s)
-    TORCH_CHECK(hi <= ss.s[s].out || lo >= ss.s[s].out + ss.s[s].n, "fused AMP-SGD: slab regions overlap");
-  SlabSrc& S = ss.s[ss.ns++];
+  SlabSrc S;
   S.slab = slab.data_ptr<float>();
   S.out = out.data_ptr<float>();
   S.rows = (int)(slab.numel() / ncol);
   S.n = (int)ncol;
-  S.groups = groups;
-  S.chunks = chunks;
-  S.nblk = (int)((ncol + cols - 1) / cols);
-  S.wait = wait;
-  S.wait_n = wait_n;
+  S.nblk = (int)((ncol + SLAB_CC - 1) / SLAB_CC);
+  return S;
 }
 
 }  // namespace opt

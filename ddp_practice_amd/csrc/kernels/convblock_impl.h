@@ -89,12 +89,6 @@ __host__ __device__ constexpr int conv5x5_win_rows(int H, int W, int nsplit, boo
   }
   return mx;
 }
-// DPA_CONV2_WHOLE_IMAGE: the fused conv2 kernels stage the whole image in every split (A/B builds)
-#ifdef DPA_CONV2_WHOLE_IMAGE
-constexpr bool kConv2RowWindow = false;
-#else
-constexpr bool kConv2RowWindow = true;
-#endif
 
 // ---------------------------------------------------------------------------
 // Staging helpers.  Every global->LDS staging loop is split into "issue every
@@ -707,15 +701,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   static_assert(PRO != 3 || (CIN == 1 && MODE != 2), "PRO 3 gathers single-channel input images");
   static_assert(EPI == 0 || MODE == 2, "EPI 1 is a data-grad epilogue");
   constexpr int NCH = CIN >= 8 ? CIN / 8 : 1;              // 16-B groups per pixel
-#ifdef DPA_IMG_PAD8
-  // 32-B pixels (CIN 16): pad rows to W + 8 so a row wrap shifts the pixel index by a
-  // multiple of 8 (one 256-B bank row) and read unswizzled: the 16 lanes of a
-  // ds_read_b128 group then hit 16 distinct 16-B slots (experiment build)
-  constexpr bool PAD8 = NCH == 2;
-#else
-  constexpr bool PAD8 = false;
-#endif
-  constexpr int HP = H + 4, WPD = W + (PAD8 ? 8 : 4);
+  constexpr int HP = H + 4, WPD = W + 4;
   constexpr int K = 25 * CIN;
   constexpr int KP = ceil_to(K, 32);
   constexpr int KS = KP / 32;
@@ -725,7 +711,6 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   constexpr int MT = (HW + 15) / 16;
   typedef MM<T> mm;
 
-  static_assert(!DYN || !PAD8, "dynamic tiles: unpadded image rows (conv5x5_img_bytes)");
   T* img;
   T* wl;
   if constexpr (DYN) {
@@ -744,7 +729,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   // (conv2 dgrad: SQ_LDS_BANK_CONFLICT -54 %)
   constexpr int PPB = NCH <= 16 ? 16 / NCH : 1;            // pixels per 256-B bank row
   auto imo = [](int px, int c) -> int {
-    if constexpr (NCH <= 1 || PAD8) {
+    if constexpr (NCH <= 1) {
       return px * CIN + c;
     } else {
       return px * CIN + ((((c >> 3) ^ ((px / PPB) & (NCH - 1)))) << 3) + (c & 7);
@@ -1449,8 +1434,6 @@ bwd_elemt_kernel(const T* __restrict__ dp, const T* __restrict__ p, const uint8_
 // ---------------------------------------------------------------------------
 // PRO 2: dy is produced on the fly from the pooled grad of the next block
 // (bin: backward through MaxPool -> ReLU -> BN); needs ROWS == H.
-// WT: the partial row is stored write-through (sc1) for an in-launch reduction
-// (MI355X_MICROARCH.md "Valid forms" row 1; convnet_fused.hip wgrad1_reduce_kernel).
 // NSL > 0: output slices instead of row chunks.  One workgroup per (image b, 16-channel
 // output tile mt, input-channel slice j of NSL) keeps the whole image as its K range
 // (ROWS == H, PRO 2) and writes the 16 x (N / NSL) block [mt*16 .. +16][j*CIN/NSL .. ) of
@@ -1478,22 +1461,18 @@ struct WgradLds {
   static constexpr size_t bytes = o_wt + sizeof(float) * (STAGE ? (size_t)CL * NS : 4);
 };
 
-template <typename T, int CIN, int COUT, int H, int W, int ROWS, int PRO = 0, bool WT = false, bool CHK = false,
-          bool DYN = false, int NSL = 0>
+template <typename T, int CIN, int COUT, int H, int W, int ROWS, int PRO = 0, bool CHK = false, bool DYN = false,
+          int NSL = 0>
 __device__ __forceinline__ void
 conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ wslab, int nsplit,
                    const BwdIn<T>& bin, const int bid) {
-  auto put = [](float* p, float v) {
-    if constexpr (WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-  };
   static_assert(PRO == 0 || (PRO == 2 && ROWS % 2 == 0), "PRO 2 works on whole 2x2 pooling windows");
   constexpr int WP = ceil_to(W, 8);
   static_assert((ROWS * WP) % 32 == 0, "ROWS*WP must be a multiple of 32");
   constexpr int KSTEPS = ROWS * WP / 32;
   constexpr int N = CIN * 25;
   constexpr bool SL = NSL > 0;  // output slices (one slab row per image), see WgradLds
-  static_assert(!SL || (PRO == 2 && ROWS == H && CIN >= 16 && CIN % NSL == 0 && COUT % 16 == 0 && !WT && !CHK),
+  static_assert(!SL || (PRO == 2 && ROWS == H && CIN >= 16 && CIN % NSL == 0 && COUT % 16 == 0 && !CHK),
                 "output slices: whole image, dy produced on the fly, ci-fastest columns");
   constexpr int CL = SL ? 16 : COUT;         // output channels staged by this workgroup
   constexpr int CIS = SL ? CIN / NSL : CIN;  // input channels staged by this workgroup
@@ -1690,7 +1669,7 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
     }
     a = group_sum<TPC>(a);  // VALU lane moves (every lane active here)
     if (sub == 0 && sl == 0) {
-      put(&row_out[COUT * N + mt0 * 16 + co], a);
+      row_out[COUT * N + mt0 * 16 + co] = a;
       // the bias column is summed by the AMP step like the weight columns: same row bound
       if (rchk) bin.chk.flag(GradChk::bad(a, bin.chk_row_bound));
     }
@@ -1729,7 +1708,7 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         if constexpr (STAGE) wtile[(mt * 16 + 4 * q + i) * NS + nat] = acc[i];
-        else put(&row_out[(mt * 16 + 4 * q + i) * N + nat], acc[i]);
+        else row_out[(mt * 16 + 4 * q + i) * N + nat] = acc[i];
         if (rchk) bin.chk.flag(GradChk::bad(acc[i], bin.chk_row_bound));
       }
     }
@@ -1746,8 +1725,6 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
         *reinterpret_cast<f32x4*>(&row_out[(mt0 * 16 + rr) * N + sl * NS + 4 * c4]) =
             *reinterpret_cast<const f32x4*>(&wtile[rr * NS + 4 * c4]);
       }
-    } else if constexpr (WT) {  // 4-B write-through stores, consecutive lanes on consecutive words
-      for (int e = tid; e < COUT * N; e += NTHR) put(&row_out[e], wtile[e]);
     } else {
       for (int e = tid; e < COUT * N / 4; e += NTHR)
         *reinterpret_cast<f32x4*>(&row_out[4 * e]) = *reinterpret_cast<const f32x4*>(&wtile[4 * e]);

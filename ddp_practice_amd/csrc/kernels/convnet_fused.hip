@@ -7,10 +7,12 @@
 //   forward   gather | conv1 (+BN1 sums) | [BN1-ReLU-pool1 -> conv2 (+BN2 sums)]
 //             | [BN2-ReLU-pool2 -> fc] -> logits                          (3 launches)
 //   backward  [fc bwd -> dp2 (+BN2 sums: complete per channel)]
-//             | [BN2/ReLU2/pool2 bwd -> conv2 dgrad -> dp1 (+BN1 partial sums)]
-//             | [BN2/ReLU2/pool2 bwd -> conv2 wgrad]        (independent of dgrad)
+//             | {[BN2/ReLU2/pool2 bwd -> conv2 dgrad -> dp1 (+BN1 partial sums)],
+//                [BN2/ReLU2/pool2 bwd -> conv2 wgrad]}: two roles of one launch (conv2_bwd)
 //             | [BN1/ReLU1/pool1 bwd -> conv1 wgrad]
-//             | weight-grad sums                                        (5 launches)
+//             | weight-grad sums                                        (4 launches)
+//   with an optimizer that sums the conv1 slab in its own launch (a slab sink): the conv1
+//   launch also sums the conv2 slab (conv1_wgrad_slab2) and no sum launch follows (3).
 //
 // (reference model: /root/reference/origin_main.py:9-31.)  With SyncBN the
 // partial sums are all-reduced between the launches (host side).  Everything
@@ -19,7 +21,6 @@
 
 #include "convblock_impl.h"
 #include "comm/xgmi.h"
-#include "kernels/amp_step.h"
 
 namespace dpa {
 namespace cnf {
@@ -270,7 +271,7 @@ template <int NSPLIT, bool EVEN>
 constexpr int conv2_wr() {
   constexpr int need = cb::conv5x5_win_rows(14, 14, NSPLIT, EVEN);
   static_assert(need > 0, "conv2: more workgroups per image than 16-pixel tiles");
-  return cb::kConv2RowWindow && need < 14 ? need : 14;
+  return need < 14 ? need : 14;
 }
 static void conv2_row_window(int wr, int nsplit, bool even, const char* what) {
   const int need = cb::conv5x5_win_rows(14, 14, nsplit, even);
@@ -542,16 +543,14 @@ void conv2_dgrad(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx
 // The weight-grad role is decomposed by OUTPUT SLICE: a workgroup is (image, 16-channel
 // output tile, input-channel slice of WG2_NSL) with the whole image as its K range
 // (cb::conv5x5_wgrad_body NSL), 2 * WG2_NSL workgroups per image, and an image yields ONE
-// slab row: wslab2 is [B][12832] fp32.  DPA_WG2_NSL=0 builds the row-chunk decomposition
-// instead (WG2_ROWS_-row chunks of one image, every chunk a full 12832-float row: 4 B rows).
+// slab row: wslab2 is [B][12832] fp32.
 #ifndef DPA_WG2_NSL
 #define DPA_WG2_NSL 2
 #endif
 constexpr int WG2_NSL = DPA_WG2_NSL;
-static_assert(WG2_NSL == 0 || WG2_NSL == 1 || WG2_NSL == 2, "conv2 weight gradient: 0 (row chunks), 1 or 2 slices");
-constexpr int WG2_ROWS_ = 4;
+static_assert(WG2_NSL == 1 || WG2_NSL == 2, "conv2 weight gradient: 1 or 2 input-channel slices");
 constexpr int WG1_ROWS_ = 4;
-constexpr int WG2_PER_IMG = WG2_NSL > 0 ? 2 * WG2_NSL : (14 + WG2_ROWS_ - 1) / WG2_ROWS_;
+constexpr int WG2_PER_IMG = 2 * WG2_NSL;
 int64_t wgrad_bn_rows(int64_t layer, int64_t B);
 // workgroups of the conv2 weight-gradient role (its grid share, site grid and residency)
 static int64_t wgrad2_wgs(int64_t B) { return B * WG2_PER_IMG; }
@@ -560,16 +559,11 @@ static int64_t wgrad2_wgs(int64_t B) { return B * WG2_PER_IMG; }
 template <typename T, bool DYN>
 __device__ __forceinline__ void conv2_wgrad_role(const T* __restrict__ p1, float* __restrict__ wslab2,
                                                  const BwdIn<T>& bi_w, int bid) {
-  if constexpr (WG2_NSL > 0)
-    cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, 14, 2, false, false, DYN, WG2_NSL>(p1, nullptr, wslab2, WG2_PER_IMG,
-                                                                                bi_w, bid);
-  else
-    cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, WG2_ROWS_, 2, false, false, DYN>(p1, nullptr, wslab2, WG2_PER_IMG,
-                                                                              bi_w, bid);
+  cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, 14, 2, false, DYN, WG2_NSL>(p1, nullptr, wslab2, WG2_PER_IMG, bi_w, bid);
 }
 template <typename T>
 constexpr size_t conv2_wgrad_lds() {
-  return cb::WgradLds<T, 16, 32, 14, 14, (WG2_NSL > 0 ? 14 : WG2_ROWS_), WG2_NSL>::bytes;
+  return cb::WgradLds<T, 16, 32, 14, 14, 14, WG2_NSL>::bytes;
 }
 template <typename T>
 __global__ void __launch_bounds__(cb::NTHR)
@@ -860,7 +854,7 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
 constexpr int WG1_ROWS = WG1_ROWS_;  // layer 1 (28 rows): 7 chunks per image
 int64_t wgrad_bn_rows(int64_t layer, int64_t B) {
   TORCH_CHECK(layer == 1 || layer == 2);
-  return B * (layer == 1 ? (28 + WG1_ROWS - 1) / WG1_ROWS : (WG2_NSL > 0 ? 1 : WG2_PER_IMG));
+  return B * (layer == 1 ? (28 + WG1_ROWS - 1) / WG1_ROWS : 1);
 }
 
 void conv_wgrad_bn(at::Tensor x, at::Tensor y, at::Tensor dp, at::Tensor idx, at::Tensor fstats, at::Tensor gsum,
@@ -894,161 +888,22 @@ void conv_wgrad_bn(at::Tensor x, at::Tensor y, at::Tensor dp, at::Tensor idx, at
   DPA_CHECK_LAUNCH();
 }
 
-
-// ---------------------------------------------------------------------------
-// The last backward launch: conv1 weight-grad partials AND every weight-grad
-// column sum, so no separate reduction launch follows.
-//   role A, workgroups [0, nwg1): BN1 bwd -> conv1 wgrad partial row (write-
-//     through), then a two-level in-launch reduction: the last arriver of each
-//     group of RG rows sums them into a group row; the last group sums the group
-//     rows into [dW1 | db1] (tickets on self-resetting counters: graph-replayable).
-//   role B, workgroups [nwg1, grid): column sums of the conv2 weight-grad slab
-//     (written by the previous launch) into [dW2 | db2], RB_COLS columns each.
-// Reference op: /root/reference/origin_main.py:13 (conv1 weight/bias grads),
-// :19 (conv2's); replaces conv_wgrad_bn + slab_reduce (one launch and one
-// kernel boundary less per step).
-// ---------------------------------------------------------------------------
-constexpr int RG = 16;        // role A: rows per group
-constexpr int RB_COLS = 32;   // role B: columns per workgroup (8 row groups of 32 lanes)
-
-__device__ __forceinline__ float ld_sc1(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// rows x n (row-major) -> out[n]: column sums in row order 0.. (deterministic)
-__device__ __forceinline__ void colsum_sc1(const float* __restrict__ src, int rows, int n, float* __restrict__ out,
-                                           bool wt) {
-  for (int j = threadIdx.x; j < n; j += cb::NTHR) {
-    float a = 0.f;
-    int r = 0;
-    for (; r + 7 < rows; r += 8) {
-      float v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = ld_sc1(src + (size_t)(r + k) * n + j);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) a += v[k];
-    }
-    for (; r < rows; ++r) a += ld_sc1(src + (size_t)r * n + j);
-    if (wt) __hip_atomic_store(out + j, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else out[j] = a;
-  }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(cb::NTHR)
-wgrad1_reduce_kernel(const T* __restrict__ x, float* __restrict__ wslab1, float* __restrict__ gslab1,
-                     float* __restrict__ out1, BwdIn<T> bi, int nwg1, const float* __restrict__ wslab2, int rows2,
-                     int n2, float* __restrict__ out2, int* __restrict__ cnt) {
-  constexpr int N1 = 16 * 25 + 16;
-  __shared__ int last_s;
-  const int tid = threadIdx.x;
-  if ((int)blockIdx.x >= nwg1) {
-    // role B: RB_COLS columns of the conv2 slab, 8 row groups of 32 lanes, fixed-order sums
-    __shared__ float part[8][RB_COLS + 1];
-    const int c0 = ((int)blockIdx.x - nwg1) * RB_COLS;
-    const int col = c0 + (tid % RB_COLS), g = tid / RB_COLS;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (col < n2) {
-      int r = g;
-      for (; r + 3 * 8 < rows2; r += 4 * 8) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] += wslab2[(size_t)(r + 8 * k) * n2 + col];
-      }
-      for (; r < rows2; r += 8) a[0] += wslab2[(size_t)r * n2 + col];
-    }
-    part[g][tid % RB_COLS] = (a[0] + a[1]) + (a[2] + a[3]);
-    __syncthreads();
-    if (tid < RB_COLS && c0 + tid < n2) {
-      float t = 0.f;
-#pragma unroll
-      for (int gg = 0; gg < 8; ++gg) t += part[gg][tid];
-      out2[c0 + tid] = t;
-    }
-    return;
-  }
-  // role A
-  const int bid = blockIdx.x;
-  constexpr int ns = (28 + WG1_ROWS_ - 1) / WG1_ROWS_;
-  cb::conv5x5_wgrad_body<T, 1, 16, 28, 28, WG1_ROWS_, 2, true>(x, nullptr, wslab1, ns, bi, bid);
-  const int ng = (nwg1 + RG - 1) / RG, g = bid / RG;
-  const int grows = min(RG, nwg1 - g * RG);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this workgroup's row has left the CU
-  __syncthreads();
-  if (tid == 0)
-    last_s = __hip_atomic_fetch_add(&cnt[g], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == grows - 1;
-  __syncthreads();
-  if (!last_s) return;
-  colsum_sc1(wslab1 + (size_t)g * RG * N1, grows, N1, gslab1 + (size_t)g * N1, true);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __hip_atomic_store(&cnt[g], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next launch
-    last_s = __hip_atomic_fetch_add(&cnt[ng], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ng - 1;
-  }
-  __syncthreads();
-  if (!last_s) return;
-  colsum_sc1(gslab1, ng, N1, out1, false);
-  if (tid == 0) __hip_atomic_store(&cnt[ng], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-int64_t wgrad1_counters(int64_t B) { return (wgrad_bn_rows(1, B) + RG - 1) / RG + 1; }
-
-// BN1 bwd -> conv1 wgrad, + the column sums of both weight-grad slabs:
-// out1 = [dW1 | db1] (416 floats), out2 = [dW2 | db2] (12832 floats).
-// cnt: int32[wgrad1_counters(B)], zeroed once (the kernel re-arms it).
-void wgrad1_reduce(at::Tensor x, at::Tensor y1, at::Tensor dp1, at::Tensor idx1, at::Tensor fstats1, at::Tensor gsum,
-                   c10::optional<at::Tensor> lsum, at::Tensor g1, double eps1, at::Tensor dg1, at::Tensor dbe1,
-                   at::Tensor wslab1, at::Tensor gslab1, at::Tensor out1, at::Tensor wslab2, at::Tensor out2,
-                   at::Tensor cnt, XcPtr xc) {
-  DPA_CHECK_INPUT(x); DPA_CHECK_INPUT(y1); DPA_CHECK_INPUT(wslab1); DPA_CHECK_INPUT(wslab2); DPA_CHECK_INPUT(cnt);
-  const int B = (int)y1.size(0);
-  TORCH_CHECK(x.size(1) == 1 && y1.size(1) == 16 && y1.size(2) == 28 && x.scalar_type() == y1.scalar_type());
-  const int nwg1 = (int)wgrad_bn_rows(1, B), ng = (nwg1 + RG - 1) / RG;
-  constexpr int N1 = 16 * 25 + 16, N2 = 32 * 400 + 32;
-  const int rows2 = (int)wgrad_bn_rows(2, B);
-  TORCH_CHECK(wslab1.numel() == (int64_t)nwg1 * N1 && gslab1.numel() >= (int64_t)ng * N1 && out1.numel() == N1,
-              "wgrad1_reduce: conv1 slab sizes");
-  TORCH_CHECK(wslab2.numel() == (int64_t)rows2 * N2 && out2.numel() == N2, "wgrad1_reduce: conv2 slab sizes");
-  TORCH_CHECK(cnt.scalar_type() == at::kInt && cnt.numel() >= ng + 1, "wgrad1_reduce: counters");
-  if (B == 0) return;
-  const int nred = (N2 + RB_COLS - 1) / RB_COLS;
-  with_t(dt_of(y1), [&](auto tag) {
-    typedef decltype(tag) T;
-    BwdIn<T> bi = bwd_in<T>(dp1, idx1, y1, fstats1, gsum, lsum, g1, eps1, 16, dg1, dbe1);
-    if (xc) {
-      TORCH_CHECK(!lsum.has_value(), "fused SyncBN exchange: gsum must be this rank's rows (no lsum)");
-      bi.xs = site_of(xc, xgmi::kSiteBwd1);
-      xgmi::set_site_grid(bi.xs, nwg1, "wgrad1_reduce");  // the reduction workgroups take no tickets
-    }
-    hipLaunchKernelGGL(wgrad1_reduce_kernel<T>, dim3(nwg1 + nred), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x),
-                       wslab1.data_ptr<float>(), gslab1.data_ptr<float>(), out1.data_ptr<float>(), bi, nwg1,
-                       wslab2.data_ptr<float>(), rows2, N2, out2.data_ptr<float>(), cnt.data_ptr<int>());
-  });
-  DPA_CHECK_LAUNCH();
-}
-
 // BN1 bwd -> conv1 weight-grad partial rows (wslab1) AND, in extra workgroups, the
 // column sums of the conv2 weight-grad slab into [dW2 | db2] (independent work that
 // fills the CUs the 224 conv1 workgroups leave idle).  The conv1 slab's own column
 // sums are left to the consumer: the fused AMP-SGD launch (optim.hip SlabSrc) or a
 // slab_reduce launch.  A reduction workgroup owns SLAB2_K chunks of 16 columns (the conv2
-// slab has one row per image: few rows per lane, so more columns per lane instead);
-// DPA_SLAB2_CHUNKS=1: one chunk each (cb::slab_reduce_body), the same sums bitwise.
-#ifndef DPA_SLAB2_CHUNKS
-#define DPA_SLAB2_CHUNKS 4
-#endif
-constexpr int SLAB2_K = DPA_SLAB2_CHUNKS;
+// slab has one row per image: few rows per lane, so more columns per lane instead).
+constexpr int SLAB2_K = 4;
 template <typename T>
 __global__ void __launch_bounds__(cb::NTHR)
 wgrad1_slab2_kernel(const T* __restrict__ x, float* __restrict__ wslab1, BwdIn<T> bi, int nwg1,
                     const float* __restrict__ wslab2, int rows2, int n2, float* __restrict__ out2, GradChk rc) {
   constexpr int ns = (28 + WG1_ROWS_ - 1) / WG1_ROWS_;
   if ((int)blockIdx.x < nwg1)
-    cb::conv5x5_wgrad_body<T, 1, 16, 28, 28, WG1_ROWS_, 2, false, true>(x, nullptr, wslab1, ns, bi, (int)blockIdx.x);
-  else if constexpr (SLAB2_K > 1)
-    cb::slab_reduce_chunks_body<SLAB2_K>(wslab2, rows2, n2, out2, (int)blockIdx.x - nwg1, rc);
+    cb::conv5x5_wgrad_body<T, 1, 16, 28, 28, WG1_ROWS_, 2, true>(x, nullptr, wslab1, ns, bi, (int)blockIdx.x);
   else
-    cb::slab_reduce_body(nullptr, 0, 0, nullptr, wslab2, rows2, n2, out2, (int)blockIdx.x - nwg1, rc);
+    cb::slab_reduce_chunks_body<SLAB2_K>(wslab2, rows2, n2, out2, (int)blockIdx.x - nwg1, rc);
 }
 
 void conv1_wgrad_slab2(at::Tensor x, at::Tensor y1, at::Tensor dp1, at::Tensor idx1, at::Tensor fstats1,
@@ -1087,154 +942,6 @@ void conv1_wgrad_slab2(at::Tensor x, at::Tensor y1, at::Tensor dp1, at::Tensor i
   DPA_CHECK_LAUNCH();
 }
 
-// ---------------------------------------------------------------------------
-// The ConvNet's optimizer step with the conv1 weight gradient inside it: ONE launch
-// instead of [conv1 wgrad + conv2 column sums] and [fused AMP step] (optim/sgd.py
-// defer_wgrad1: the backward leaves conv1's weight gradient to the optimizer, which
-// computes it in its own launch -- the update still happens in scaler.step()).
-//   workgroups [0, nw1): producers -- BN1 backward -> conv1 weight-gradient partial row,
-//     stored write-through, then one arrival on w1cnt;
-//   workgroups [nw1, grid): the fused AMP step (csrc/kernels/amp_step.h) with three
-//     slab sources: BN1's [dbeta1 | dgamma1] from the conv2 backward's partial sums,
-//     conv1's [dW1 | db1] (its owners wait for the producers' arrivals) and conv2's
-//     [dW2 | db2] (written by the previous launch: summed at once).
-// Producers come first in the grid, so the in-order dispatcher places all of them before
-// any AMP workgroup: a waiting owner can never hold a slot a producer needs.
-// Reference: /root/reference/ddp_main.py:91-93 (backward, scaler.step, update) and
-// origin_main.py:13-14 (conv1 / BN1, whose gradients these are).
-// ---------------------------------------------------------------------------
-constexpr int CAS_U = 2;  // granules per lane of the AMP workgroups (keeps the AMP grid <= one per CU)
-
-template <typename T, bool XG>
-__global__ void __launch_bounds__(cb::NTHR)
-convnet_amp_step_kernel(const T* __restrict__ x, float* __restrict__ wslab1, BwdIn<T> bi, int nw1,
-                        int* __restrict__ w1cnt, opt::MTList L, float* __restrict__ scale, int* __restrict__ tracker,
-                        float* __restrict__ found_inf, unsigned long long* __restrict__ sync, float lr, float momentum,
-                        float dampening, float wd, int nesterov, int maximize, float growth, float backoff,
-                        int interval, xgmi::XSite xg, int* __restrict__ err, long long barrier_ticks, opt::SlabSet ss,
-                        int grid_amp) {
-  const int bid = (int)blockIdx.x;
-  DPA_STAMP(0);
-  if (bid < nw1) {
-    constexpr int ns = (28 + WG1_ROWS_ - 1) / WG1_ROWS_;
-    cb::conv5x5_wgrad_body<T, 1, 16, 28, 28, WG1_ROWS_, 2, true>(x, nullptr, wslab1, ns, bi, bid);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this workgroup's row has left the CU
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(w1cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    DPA_STAMP(8);
-    return;
-  }
-  opt::amp_sgd_body<CAS_U, XG>(L, scale, tracker, found_inf, sync, lr, momentum, dampening, wd, nesterov, maximize,
-                               growth, backoff, interval, xg, err, barrier_ticks, ss, grid_amp, bid - nw1);
-}
-
-// Launch shape of convnet_amp_step at batch B: (producers, AMP workgroups).
-static std::pair<int, int> cas_shape(int64_t B, int64_t n_params_granules) {
-  const int nw1 = (int)wgrad_bn_rows(1, B);
-  const int nreg = (int)std::max<int64_t>(1, (n_params_granules + opt::FUSED_THR * CAS_U - 1) / (opt::FUSED_THR * CAS_U));
-  const int s0 = 1, s1 = (16 * 25 + 16 + 15) / 16, s2 = (32 * 400 + 32 + 63) / 64;
-  return {nw1, nreg + s0 + s1 + s2};
-}
-
-// The AMP workgroups of the launch are co-resident (they meet at a grid barrier) and the
-// producers of one XCD fit beside them once they are done.
-bool convnet_amp_step_ok(int64_t B, int64_t n_params_granules, at::ScalarType st) {
-  const auto sh = cas_shape(B, n_params_granules);
-  bool ok = true;
-  with_t(dt_of(at::empty({0}, at::TensorOptions().dtype(st))), [&](auto tag) {
-    typedef decltype(tag) T;
-    if constexpr (std::is_same<T, float>::value) {
-      ok = false;  // fp32: no scaler in the reference path; the separate launches stay
-    } else {
-      ok = co_resident(reinterpret_cast<const void*>(&convnet_amp_step_kernel<T, false>), sh.second, cb::NTHR, 0) &&
-           co_resident(reinterpret_cast<const void*>(&convnet_amp_step_kernel<T, true>), sh.second, cb::NTHR, 0) &&
-           co_resident(reinterpret_cast<const void*>(&convnet_amp_step_kernel<T, false>), sh.first, cb::NTHR, 0);
-    }
-  });
-  // with the xGMI engine both the conv1 BN site (sh.first workgroups) and the gradient
-  // site (sh.second) ride this launch: each must fit its epoch words (comm/xgmi.h)
-  return ok && xgmi::site_grid_fits(sh.first) && xgmi::site_grid_fits(sh.second);
-}
-
-// params / grads / bufs / first / lr ... sync / xc: as optim.amp_sgd_fused (one param group).
-// conv1: x (batch images), y1, dp1, idx1, fstats1, gsum1 (BN1 backward sum rows; all-reduced
-// under a host SyncBN), g1, eps1 -> wslab1 (partial rows), w1cnt (int32, zeroed once),
-// out1 = [dW1 | db1]; bn1: the BN1 sum rows of this rank ([S1 | S2] per row) -> out0 =
-// [dbeta1 | dgamma1]; conv2: wslab2 -> out2 = [dW2 | db2].
-void convnet_amp_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, std::vector<at::Tensor> bufs,
-                      double lr, double momentum, double dampening, double wd, bool nesterov, bool maximize,
-                      std::vector<int64_t> first, at::Tensor scale, at::Tensor tracker, at::Tensor found_inf,
-                      double growth, double backoff, int64_t interval, at::Tensor sync, XcPtr xc, at::Tensor x,
-                      at::Tensor y1, at::Tensor dp1, at::Tensor idx1, at::Tensor fstats1, at::Tensor gsum1,
-                      at::Tensor g1, double eps1, at::Tensor wslab1, at::Tensor w1cnt, at::Tensor out1, at::Tensor bn1,
-                      at::Tensor out0, at::Tensor wslab2, at::Tensor out2) {
-  DPA_CHECK_INPUT(x); DPA_CHECK_INPUT(y1); DPA_CHECK_INPUT(wslab1); DPA_CHECK_INPUT(wslab2); DPA_CHECK_INPUT(w1cnt);
-  const int B = (int)y1.size(0);
-  TORCH_CHECK(x.size(1) == 1 && y1.size(1) == 16 && y1.size(2) == 28 && x.scalar_type() == y1.scalar_type());
-  TORCH_CHECK(w1cnt.scalar_type() == at::kInt && w1cnt.numel() >= 1, "convnet_amp_step: w1cnt int32[1]");
-  TORCH_CHECK(sync.is_cuda() && sync.scalar_type() == at::kLong && sync.is_contiguous(),
-              "convnet_amp_step: sync must be a zero-initialised int64 device tensor");
-  TORCH_CHECK(scale.scalar_type() == at::kFloat && found_inf.scalar_type() == at::kFloat &&
-              tracker.scalar_type() == at::kInt);
-  constexpr int N1 = 16 * 25 + 16, N2 = 32 * 400 + 32;
-  const int nw1 = (int)wgrad_bn_rows(1, B);
-  TORCH_CHECK(wslab1.numel() == (int64_t)nw1 * N1 && out1.numel() == N1, "convnet_amp_step: conv1 slab sizes");
-  TORCH_CHECK(wslab2.numel() == wgrad_bn_rows(2, B) * N2 && out2.numel() == N2, "convnet_amp_step: conv2 slab sizes");
-  TORCH_CHECK(out0.numel() == 32 && bn1.numel() % 32 == 0, "convnet_amp_step: BN1 sum rows [rows][32] -> 32");
-  if (B == 0) return;
-  opt::MTList L = opt::fused_list(params, grads, bufs, first, momentum);
-  opt::SlabSet ss;
-  // the flush path's associations (bitwise the same gradients): BN1 sums as cb::colsum_rows
-  // (2C = 32 columns, G = 8), the weight-gradient slabs as slab_reduce (G = 16)
-  opt::add_slab(ss, L, bn1, out0, 8, 1, nullptr, 0);
-  opt::add_slab(ss, L, wslab1, out1, 16, 1, w1cnt.data_ptr<int>(), nw1);
-  opt::add_slab(ss, L, wslab2, out2, 16, 4, nullptr, 0);
-  ss.rearm = w1cnt.data_ptr<int>();
-  ss.blanes = 8;  // ~240 arriving workgroups: arrivals spread over 8 words
-  TORCH_CHECK(sync.numel() >= 1 + 2 * ss.blanes * opt::kBarStride, "convnet_amp_step: sync must hold ",
-              1 + 2 * ss.blanes * opt::kBarStride, " int64");
-  const auto sh = cas_shape(B, L.chunk_off[L.n]);
-  int nslab = 0;
-  for (int s = 0; s < ss.ns; ++s) nslab += ss.s[s].nblk;
-  const int nreg = (int)std::max<int64_t>(1, (L.chunk_off[L.n] + opt::FUSED_THR * CAS_U - 1) / (opt::FUSED_THR * CAS_U));
-  const int grid_amp = nreg + nslab;
-  TORCH_CHECK(grid_amp == sh.second && nw1 == sh.first, "convnet_amp_step: launch shape");
-  constexpr double kBarrierSeconds = 10.0;
-  with_t(dt_of(y1), [&](auto tag) {
-    typedef decltype(tag) T;
-    if constexpr (std::is_same<T, float>::value) {
-      TORCH_CHECK(false, "convnet_amp_step: bf16 / fp16 only");
-    } else {
-      // producers: BN1 backward from the rows, no dgamma / dbeta (the BN1 slab source owns them)
-      BwdIn<T> bi = bwd_in<T>(dp1, idx1, y1, fstats1, gsum1, c10::nullopt, g1, eps1, 16, c10::nullopt,
-                              c10::nullopt);
-      if (xc) {
-        bi.xs = site_of(xc, xgmi::kSiteBwd1);
-        xgmi::set_site_grid(bi.xs, nw1, "convnet_amp_step conv1 weight gradient");
-      }
-      xgmi::XSite xg;
-      if (xc) {
-        xg = xc->grad_site();
-        TORCH_CHECK(L.chunk_off[L.n] * 4 <= xg.max_vals, "convnet_amp_step: too many elements for the xGMI engine");
-        xgmi::set_site_grid(xg, grid_amp, "convnet_amp_step");
-      }
-      auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(nw1 + grid_amp), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x),
-                           wslab1.data_ptr<float>(), bi, nw1, w1cnt.data_ptr<int>(), L, scale.data_ptr<float>(),
-                           tracker.data_ptr<int>(), found_inf.data_ptr<float>(),
-                           reinterpret_cast<unsigned long long*>(sync.data_ptr<int64_t>()), (float)lr,
-                           (float)momentum, (float)dampening, (float)wd, (int)nesterov, (int)maximize, (float)growth,
-                           (float)backoff, (int)interval, xg,
-                           reinterpret_cast<int*>(sync.data_ptr<int64_t>() + sync.numel() - 1),
-                           (long long)(kBarrierSeconds * 1e8), ss, grid_amp);
-      };
-      if (xc) go(convnet_amp_step_kernel<T, true>);
-      else go(convnet_amp_step_kernel<T, false>);
-    }
-  });
-  DPA_CHECK_LAUNCH();
-}
-
 // Whether every launch that exchanges SyncBN sums in-kernel (comm/xsite.h: all
 // of its workgroups poll the peers' rows) is co-resident at batch B; if not,
 // ops/convnet_fused.py all-reduces between the launches instead.
@@ -1266,7 +973,6 @@ bool sites_resident(int64_t B, at::ScalarType st) {
     chk(reinterpret_cast<const void*>(&conv2_wgrad_kernel<T>), wgrad2_wgs(B));
     chk(reinterpret_cast<const void*>(&cb::conv5x5_wgrad_kernel<T, 1, 16, 28, 28, WG1_ROWS, 2>),
         wgrad_bn_rows(1, B));
-    chk(reinterpret_cast<const void*>(&wgrad1_reduce_kernel<T>), wgrad_bn_rows(1, B));
     chk(reinterpret_cast<const void*>(&wgrad1_slab2_kernel<T>), wgrad_bn_rows(1, B));
   });
   return ok;
@@ -1307,11 +1013,7 @@ void register_convnet_fused(pybind11::module& m) {
   s.def("wgrad_bn_rows", &cnf::wgrad_bn_rows);
   s.def("sites_resident", &cnf::sites_resident);
   s.def("fwd2_split", &cnf::fwd2_split, py::arg("fp32"));
-  s.def("wgrad1_reduce", &cnf::wgrad1_reduce);
   s.def("conv1_wgrad_slab2", &cnf::conv1_wgrad_slab2);
-  s.def("convnet_amp_step", &cnf::convnet_amp_step);
-  s.def("convnet_amp_step_ok", &cnf::convnet_amp_step_ok);
-  s.def("wgrad1_counters", &cnf::wgrad1_counters);
 }
 
 }  // namespace dpa

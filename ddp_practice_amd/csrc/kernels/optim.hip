@@ -112,13 +112,13 @@ __global__ void update_scale_kernel(float* scale, int* tracker, float* found_inf
 
 // GradScaler.step + SGD + GradScaler.update in ONE launch over a small grid (the
 // ConvNet: 29,034 floats), csrc/kernels/amp_step.h amp_sgd_body.  One optional slab
-// source (ss.ns <= 1): the ConvNet's conv1 weight-gradient slab (optim/sgd.py defer_slab).
+// source (ss.nblk > 0): the ConvNet's conv1 weight-gradient slab (optim/sgd.py defer_slab).
 template <int U, bool XG, int THR = FUSED_THR>
 __global__ void __launch_bounds__(THR)
 amp_sgd_fused_kernel(MTList L, float* __restrict__ scale, int* __restrict__ tracker, float* __restrict__ found_inf,
                      unsigned long long* __restrict__ sync, float lr, float momentum, float dampening, float wd,
                      int nesterov, int maximize, float growth, float backoff, int interval,
-                     xgmi::XSite xg, int* __restrict__ err, long long barrier_ticks, SlabSet ss, int grid,
+                     xgmi::XSite xg, int* __restrict__ err, long long barrier_ticks, SlabSrc ss, int grid,
                      const int* __restrict__ chk, int nchk) {
   // grid == the launch's workgroup count, passed in: gridDim is a load from the hidden kernel
   // arguments on gfx950, and its wait at the top of the kernel came before the table loads
@@ -462,11 +462,10 @@ void amp_sgd_fused(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
   }
   TORCH_CHECK(amp_sgd_resident(), "fused AMP-SGD: grid not co-resident on this device (use the unfused step)");
   MTList L = fused_list(params, grads, bufs, first, momentum);
-  SlabSet ss;
   TORCH_CHECK(slab.has_value() == slab_out.has_value(), "fused AMP-SGD: slab and slab_out go together");
-  if (slab.has_value()) add_slab(ss, L, *slab, *slab_out, 16, 1, nullptr, 0);
+  const SlabSrc ss = slab.has_value() ? slab_src(L, *slab, *slab_out) : SlabSrc{};
   auto launch = [&](auto kern, int bg, xgmi::XSite xg) {
-    const int grid = (int)std::max<int64_t>(1, (L.chunk_off[L.n] + bg - 1) / bg) + (ss.ns ? ss.s[0].nblk : 0);
+    const int grid = (int)std::max<int64_t>(1, (L.chunk_off[L.n] + bg - 1) / bg) + ss.nblk;
     TORCH_CHECK(grid <= FUSED_MAX_BLOCKS, "fused AMP-SGD: grid exceeds the co-resident bound");
     xgmi::set_site_grid(xg, grid, "fused AMP-SGD");  // every workgroup takes a ticket (no hidden-argument load)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(FUSED_THR), 0, cur_stream(), L, sc, tr, fi,

@@ -6,9 +6,10 @@ removes launches that exist only because torch runs one module at a time:
   forward  (train): conv1(+BN1 sums, packs conv2's bf16 weight tiles) | BN1-ReLU-pool1 -> conv2 (+BN2 sums)
                     | BN2-ReLU-pool2 -> fc
                     = 3 launches for the model (per-layer ops: 6, torch: ~14 + host syncs)
-  backward:         fc bwd (+BN2 sums) | BN2 bwd -> conv2 dgrad (+BN1 sums) | BN2 bwd -> conv2 wgrad
-                    | BN1 bwd -> conv1 wgrad | weight-grad sums = 5 launches
-                    (per-layer ops: 10, torch: ~20)
+  backward:         fc bwd (+BN2 sums) | {BN2 bwd -> conv2 dgrad (+BN1 sums), BN2 bwd -> conv2 wgrad}
+                    | BN1 bwd -> conv1 wgrad | weight-grad sums = 4 launches
+                    (per-layer ops: 10, torch: ~20); with a slab sink the conv1 launch also sums
+                    the conv2 slab and the optimizer's launch the conv1 slab: 3
 
 Every BatchNorm backward is applied while staging the operand of the next
 GEMM (the conv-output gradient never exists in HBM), and its reductions are
@@ -53,38 +54,9 @@ def supported(model, x: torch.Tensor) -> bool:
 
 _RESIDENT: dict = {}
 _SPLIT_BWD2 = os.environ.get("DPA_SPLIT_BWD2", "0") == "1"
-_SPLIT_WGRAD1 = os.environ.get("DPA_SPLIT_WGRAD1", "1") == "1"  # merged launch measured slower (15.0 vs 10.9 us)
-# conv1 wgrad + conv2 slab sums in one launch even without a slab sink (A/B; then a conv1-only sum launch)
-_WGRAD1_SLAB2 = os.environ.get("DPA_WGRAD1_SLAB2", "0") == "1"
-# conv1's weight gradient deferred into the optimizer's fused launch (5 launches per step):
-# measured no faster than the two launches it merges (54.2-54.6 vs 54.1-54.2 us/step,
-# profiles/r4h_defer_wgrad1_ab.txt): the in-launch producer -> slab-owner hand-off (write-
-# through rows, arrival counter, polling) costs ~3 us, more than the kernel boundary it
-# removes; round 6, with the pre-checked step it gives up: 0.0516 vs 0.0482 ms
-# (profiles/r6az_defer_wgrad1_ab.txt).  Opt-in: DPA_DEFER_WGRAD1=1
-_DEFER_WGRAD1 = os.environ.get("DPA_DEFER_WGRAD1", "0") == "1"
 # producer-side gradient checks instead of the fused AMP step's grid barrier (single rank);
 # DPA_PRECHECK=0: the barrier (A/B runs)
 _PRECHECK = os.environ.get("DPA_PRECHECK", "1") != "0"
-_CAS_OK: dict = {}
-
-
-def _wgrad1_deferrable(B: int, dtype: torch.dtype, opt) -> bool:
-    """convnet.convnet_amp_step can run this batch size / dtype on this device (its AMP
-    workgroups co-resident) and the optimizer's step takes the small fused path.
-
-    Not for ranks sharing one GPU (DPA_SHARED_GPU=1, bench.py --share-gpu): the launch's
-    ~470 workgroups per rank wait on the peers' exchange inside the kernel, and two ranks'
-    launches do not fit the card together (a peer's workgroups could never be placed)."""
-    if os.environ.get("DPA_SHARED_GPU") == "1" and getattr(opt, "_deferred_ddp", None) is not None:
-        return False
-    if not getattr(opt, "small_fusable", lambda: False)():
-        return False
-    gran = sum((p.numel() + 3) // 4 for g in opt.param_groups for p in g["params"])
-    key = (B, dtype, gran)
-    if key not in _CAS_OK:
-        _CAS_OK[key] = bool(_load_ext().convnet.convnet_amp_step_ok(B, gran, dtype))
-    return _CAS_OK[key]
 
 
 def _fused_site_engine(comm, batch: int, dtype: torch.dtype):
@@ -147,7 +119,7 @@ def _head_step_ok(B: int, N: int, dtype: torch.dtype) -> bool:
 class ConvNetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, g1, be1, w2, b2, g2, be2, wfc, bfc, bufs, training, moms, epss, comm, cdtype,
-                labels=None, ce_cfg=(-100, 0.0), holder=None, state=None, gather=None, wcnt=None, sink=None):
+                labels=None, ce_cfg=(-100, 0.0), holder=None, state=None, gather=None, sink=None):
         cb, cn = _mods()
         rm1, rv1, nbt1, rm2, rv2, nbt2 = bufs
         m1, m2 = (-1.0 if m is None else float(m) for m in moms)
@@ -249,10 +221,8 @@ class ConvNetFn(torch.autograd.Function):
             cn.head_fwd(y2, None, fstats2, g2, be2, rm2, rv2, nbt2, m2, e2, False, wfc, bfc, logits, None, None,
                         None, None)
         ctx.training = training
-        ctx.wcnt = wcnt
         ctx.sink = sink
         ctx.w1b1 = (w1, b1) if sink is not None else None
-        ctx.l12 = (w1, b1, g1, be1, w2, b2) if sink is not None else None
         ctx.allp = (w1, b1, g1, be1, w2, b2, g2, be2, wfc, bfc) if sink is not None else None
         ctx.sync = sync
         ctx.comm = comm
@@ -312,7 +282,7 @@ class ConvNetFn(torch.autograd.Function):
         ctx.chk = ctx.chk_scale = None
         if sink0 is not None and hasattr(sink0, "set_prechecked"):
             sink0.clear_prechecked()  # an earlier backward's check no longer describes .grad
-        if not (chk is not None and fc[0] is not None and not _SPLIT_BWD2 and not _DEFER_WGRAD1
+        if not (chk is not None and fc[0] is not None and not _SPLIT_BWD2
                 and all(p.grad is None for p in ctx.allp)):
             chk = cscale = None
         # 2+3. BN2 bwd -> {conv2 dgrad -> dp1 (+ BN1 partial sums), conv2 wgrad partials}: one launch
@@ -333,57 +303,35 @@ class ConvNetFn(torch.autograd.Function):
             cn.conv2_bwd(wpk_d, y2, dp2, idx2, fstats2, gsum2, g2, e2, dp1, idx1, xh1, bslab1, p1, wslab2, xc,
                          lsum2, dgb[0], dgb[1], *fc, chk)
         # 4+5. BN1 bwd -> conv1 wgrad partials (+ dgamma1 / dbeta1 from the local sums), and the
-        #      column sums of both weight-grad slabs -> [dW1 | db1], [dW2 | db2]: one launch
-        #      (DPA_SPLIT_WGRAD1=1: wgrad launch + a separate reduction launch, A/B runs)
+        #      column sums of both weight-grad slabs -> [dW1 | db1], [dW2 | db2]
         wslab1 = torch.empty(cn.wgrad_bn_rows(1, B) * (n_w1 + 16), **f32)
         if sync and xc is None:
             gsum1, lsum1, xc1 = comm.all_reduce(bslab1), bslab1, None
         else:
             gsum1, lsum1, xc1 = bslab1, None, xc
         out1, out2 = out.narrow(0, 0, n_w1 + 16), out.narrow(0, n_w1 + 48, n_w2 + 32)
-        out0 = out.narrow(0, n_w1 + 16, 32)  # [dbeta1 | dgamma1]
         sink = ctx.sink
-        w1b1, l12 = ctx.w1b1, ctx.l12
-        ctx.w1b1 = ctx.l12 = None
+        w1b1 = ctx.w1b1
+        ctx.w1b1 = None
         if sink is not None:
             sink.flush_slab()  # an earlier backward's sums first (they may be accumulated into)
             # a gradient region is left to the optimizer's fused step only when autograd will
             # hand its views to .grad as they are (no accumulation into an existing .grad)
             if any(p.grad is not None for p in w1b1):
                 sink = None
-        if (sink is not None and _DEFER_WGRAD1 and hasattr(sink, "defer_wgrad1")
-                and all(p.grad is None for p in l12) and _wgrad1_deferrable(B, x.dtype, sink)):
-            # the conv1 weight gradient itself, BN1's and conv2's column sums: all computed
-            # inside the optimizer's fused launch (convnet.convnet_amp_step); the backward
-            # launches nothing more.  Any other gradient reader flushes first (optim.SGD)
-            # (only regions of `out` other than the returned views: a second reference to a
-            # returned gradient makes autograd copy it into .grad now, before it is computed)
-            sink.defer_wgrad1(dict(x=x, y1=y1, dp1=dp1, idx1=idx1, fstats1=fstats1, gsum1=gsum1, lsum1=lsum1, g1=g1,
-                                   e1=e1, wslab1=wslab1, out1=out1, bn1=lsum1 if lsum1 is not None else gsum1,
-                                   out0=out0, wslab2=wslab2, out2=out2, xc1=xc1))
-        elif sink is not None or _WGRAD1_SLAB2:
+        if sink is not None:
             # conv1 wgrad partials + the conv2 slab's column sums in one launch; the conv1
-            # slab's sums run inside the fused AMP-SGD launch (optim.SGD.defer_slab) or next
-            if sink is None:
-                chk = cscale = None
+            # slab's sums run inside the fused AMP-SGD launch (optim.SGD.defer_slab)
             cn.conv1_wgrad_slab2(x, y1, dp1, idx1, fstats1, gsum1, lsum1, g1, e1, dg1, dbe1, wslab1, wslab2, out2,
                                  xc1, chk)
-            if sink is not None:
-                sink.defer_slab(wslab1, out1)
-                if chk is not None:
-                    sink.set_prechecked(chk, cscale, out)
-            else:
-                cb.slab_reduce(wslab1, n_w1 + 16, out1)
-        elif _SPLIT_WGRAD1 or ctx.wcnt is None:
+            sink.defer_slab(wslab1, out1)
+            if chk is not None:
+                sink.set_prechecked(chk, cscale, out)
+        else:
             cn.conv_wgrad_bn(x, y1, dp1, idx1, fstats1, gsum1, lsum1, g1, e1, dg1, dbe1, wslab1, xc1)
             cb.slab_reduce(wslab1, n_w1 + 16, out1, wslab2, n_w2 + 32, out2)
-        else:
-            cnt = ctx.wcnt
-            gslab1 = torch.empty((cn.wgrad1_counters(B) - 1) * (n_w1 + 16), **f32)
-            cn.wgrad1_reduce(x, y1, dp1, idx1, fstats1, gsum1, lsum1, g1, e1, dg1, dbe1, wslab1, gslab1, out1,
-                             wslab2, out2, cnt, xc1)
         return (None, dw1.view(s_w1), db1, dg1, dbe1, dw2.view(s_w2), db2, dg2, dbe2, dwfc.view(s_wfc), dbfc,
-                None, None, None, None, None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 def convnet_forward(model, x, comm=None, cdtype=None):
@@ -426,17 +374,9 @@ def convnet_forward(model, x, comm=None, cdtype=None):
                 # kernel re-arms them itself, so graph replays need no reset)
                 state = torch.zeros(4, dtype=torch.int64, device=x.device)
                 model._dpa_head_state = state
-    wcnt = None
-    if training:
-        # tickets of the in-launch weight-grad reduction (zeroed once, re-armed by the kernel)
-        n = _load_ext().convnet.wgrad1_counters(x.shape[0])
-        wcnt = getattr(model, "_dpa_wgrad_cnt", None)
-        if wcnt is None or wcnt.numel() < n or wcnt.device != x.device:
-            wcnt = torch.zeros(max(n, 64), dtype=torch.int32, device=x.device)
-            model._dpa_wgrad_cnt = wcnt
     out = ConvNetFn.apply(x, c1.weight, c1.bias, bn1.weight, bn1.bias, c2.weight, c2.bias, bn2.weight, bn2.bias,
                           fc.weight, fc.bias, bufs, training, (bn1.momentum, bn2.momentum), (bn1.eps, bn2.eps),
-                          comm, cdtype, labels, (-100, 0.0), holder, state, gather, wcnt,
+                          comm, cdtype, labels, (-100, 0.0), holder, state, gather,
                           getattr(model, "_dpa_slab_sink", None) if training else None)
     if holder:
         out._dpa_pre_ce = holder.get("ce")

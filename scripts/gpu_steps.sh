@@ -42,7 +42,6 @@
 #   lpdyn_ab2    the same A/B as lpdyn_ab, more rounds, plain and forced
 #   dg4_ab       conv2 data gradient at 4 workgroups per image (experiment build _C_dg4.so)
 #   fp32dg_ab    fp32 conv2 data gradient split 4 vs 2 (experiment build _C_dgf2.so)
-#   defer_ab     conv1 weight gradient inside the optimizer launch (DPA_DEFER_WGRAD1=1) vs as built
 #   rn_knobs     ResNet-50 conv tuning knobs re-swept (wgrad blocks / min pixels, 1x1 pixel tile, stats defer)
 #   rtenv_ab     HIP runtime knobs (HIP_FORCE_DEV_KERNARG, DEBUG_CLR_GRAPH_PACKET_CAPTURE) on the driver command
 #   smoke        __graft_entry__.smoke()
@@ -180,9 +179,6 @@ step() {
     rtenv_ab)  # HIP runtime knobs on the driver's command: kernel arguments in device memory, graph packet capture
       bash scripts/ab_bench.sh "$OUT/rtenv_ab.txt" 3 "--steps 20 --warmup 5 --no-baseline --epochs 0 --extra-dtypes ," \
         base=default kd1=env:HIP_FORCE_DEV_KERNARG=1 kd0=env:HIP_FORCE_DEV_KERNARG=0 gpc0=env:DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 ;;
-    defer_ab)  # conv1 weight gradient deferred into the optimizer's launch (DPA_DEFER_WGRAD1=1) vs as built
-      bash scripts/ab_bench.sh "$OUT/defer_ab.txt" 3 "--steps 2000 --warmup 50 --no-baseline --epochs 0 --no-steady \
---extra-dtypes ," base=default defer=env:DPA_DEFER_WGRAD1=1 ;;
     rn_knobs)  # ResNet-50: re-sweep of the conv tuning knobs on this tree
       bash scripts/ab_bench.sh "$OUT/rn_knobs.txt" 2 "--model resnet50 --steps 100 --warmup 10 --no-baseline" base=default \
         wb384=env:DPA_WGRAD_BLOCKS=384 wb768=env:DPA_WGRAD_BLOCKS=768 mp512=env:DPA_WGRAD_MINPIX=512 \

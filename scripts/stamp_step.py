@@ -80,11 +80,8 @@ wrap(C.convnet_head, "head_step", lambda a: [("head_step", slice(0, 32))])
 wrap(C.convnet, "conv2_bwd", lambda a: [("conv2_bwd/dgrad", slice(0, NDG)),
                                          ("conv2_bwd/wgrad", slice(NDG, NDG + 4 * B))])
 wrap(C.convnet, "conv2_fwd", lambda a: [("conv2_fwd", slice(0, NFW))])
-wrap(C.convnet, "wgrad1_reduce", lambda a: [("wgrad1_reduce/wgrad", slice(0, 7 * B))])
 wrap(C.convnet, "conv1_wgrad_slab2", lambda a: [("wgrad1_slab2/wgrad", slice(0, 7 * B)),
                                                  ("wgrad1_slab2/sums", slice(7 * B, 512))])
-wrap(C.convnet, "convnet_amp_step", lambda a: [("amp_step/producers", slice(0, 7 * B)),
-                                                ("amp_step/amp", slice(7 * B, 512))])
 wrap(C.optim, "amp_sgd_fused", lambda a: [("amp_sgd_fused", slice(0, 512))])
 FORCED = "--forced" in sys.argv
 if FORCED:
