@@ -253,8 +253,9 @@ ce_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target, 
     const bool use = rv && t != ignore_index;
     if (use && gl == 0) {
       const float xt = (t >= 0 && t < N) ? Cvt<T>::to_f(row[t]) : NAN;  // bad target -> NaN loss
-      // (1-eps)*(lse - x_t) + eps*(lse - mean_n x_n)
-      lsum += (1.f - smoothing) * (lse - xt) + smoothing * (lse - sx / (float)N);
+      // (1-eps)*(lse - x_t) + eps*(lse - mean_n x_n); without smoothing the second term is
+      // dropped, not multiplied by 0: a masked class (-inf logit) makes sx -inf and 0 * inf NaN
+      lsum += (1.f - smoothing) * (lse - xt) + (smoothing != 0.f ? smoothing * (lse - sx / (float)N) : 0.f);
     }
     if (rv) {
       const float rs = 1.f / se;
@@ -339,7 +340,7 @@ ce_fwd_rows_kernel(const T* __restrict__ logits, const int64_t* __restrict__ tar
     const bool use = rv && t != ignore_index;
     if (use && gl == 0) {
       const float xt = (t >= 0 && t < N) ? Cvt<T>::to_f(row[t]) : NAN;  // bad target -> NaN loss
-      lsum += (1.f - smoothing) * (lse - xt) + smoothing * (lse - sx / (float)N);
+      lsum += (1.f - smoothing) * (lse - xt) + (smoothing != 0.f ? smoothing * (lse - sx / (float)N) : 0.f);
     }
     if (rv) {
       const float rs = 1.f / se;
