@@ -1,8 +1,221 @@
-// Host side of the fused conv-block kernels (device code: convblock_impl.h).
-#include "convblock_impl.h"
+// The per-layer conv-block op: its own kernels and the host side (conv kernels: conv5x5.h, conv5x5_wgrad.h).
+#include "conv5x5.h"
+#include "conv5x5_wgrad.h"
 
 namespace dpa {
 namespace cb {
+
+constexpr int kBwdSplit = 8;  // batch split of bwd_reduce
+
+// ---------------------------------------------------------------------------
+// BN finalize + normalise + ReLU + 2x2/2 max-pool (+ argmax index, first max
+// wins in (dy,dx) scan order as ATen's max_pool2d).  One thread per pooled
+// output.  Each workgroup first reduces the conv's per-workgroup partial sums
+// (nrows x (2C+1) floats, L2-resident); workgroup 0 publishes the final sums to
+// fstats and updates the running stats (momentum<0 => cumulative average).
+// ---------------------------------------------------------------------------
+template <typename T, int C, int H, int W>
+__global__ void __launch_bounds__(NTHR)
+bn_relu_pool_kernel(const T* __restrict__ y, const float* __restrict__ fslab, int nrows,
+                    float* __restrict__ fstats, const float* __restrict__ gamma, const float* __restrict__ beta,
+                    float* __restrict__ rmean, float* __restrict__ rvar, int64_t* __restrict__ nbt,
+                    float momentum, float eps, int train, T* __restrict__ p, uint8_t* __restrict__ idx,
+                    int total) {
+  constexpr int HO = H / 2, WO = W / 2;
+  constexpr int RL = 2 * C + 1;
+  __shared__ float part[NTHR];
+  __shared__ float sc_s[C], beta_s[C], mean_s[C];
+  const int tid = threadIdx.x;
+  if (train) {
+    // column j of the slab summed over rows; NTHR/RL row-groups in parallel
+    constexpr int G = NTHR / RL;  // >= 3 for C <= 32
+    static_assert(G >= 1, "C too large");
+    const int j = tid % RL, g = tid / RL;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if (g < G) {
+      int rr = g;
+      for (; rr + 3 * G < nrows; rr += 4 * G) {
+        a0 += fslab[(size_t)rr * RL + j];
+        a1 += fslab[(size_t)(rr + G) * RL + j];
+        a2 += fslab[(size_t)(rr + 2 * G) * RL + j];
+        a3 += fslab[(size_t)(rr + 3 * G) * RL + j];
+      }
+      for (; rr < nrows; rr += G) a0 += fslab[(size_t)rr * RL + j];
+    }
+    part[tid] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    if (tid < RL) {
+      float t = 0.f;
+      for (int gg = 0; gg < G; ++gg) t += part[gg * RL + tid];
+      part[tid] = t;  // each tid < RL only touches its own column's slots (gg*RL + tid)
+    }
+    __syncthreads();
+    if (tid < C) {
+      const float n = part[2 * C];
+      const float m1 = part[tid] / n;
+      const float shv = fstats[2 * C + 1 + tid];
+      const float mean = shv + m1;
+      const float var = fmaxf(part[C + tid] / n - m1 * m1, 0.f);
+      const float invstd = rsqrtf(var + eps);
+      const float s = gamma[tid] * invstd;
+      sc_s[tid] = s;
+      beta_s[tid] = beta[tid];
+      mean_s[tid] = mean;
+      if (blockIdx.x == 0) {
+        fstats[tid] = part[tid];
+        fstats[C + tid] = part[C + tid];
+        if (tid == 0) fstats[2 * C] = n;
+        const int64_t nb = nbt[0] + 1;
+        const float mom = momentum >= 0.f ? momentum : 1.f / (float)nb;
+        rmean[tid] = (1.f - mom) * rmean[tid] + mom * mean;
+        rvar[tid] = (1.f - mom) * rvar[tid] + mom * var * (n / fmaxf(n - 1.f, 1.f));
+      }
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) nbt[0] = nbt[0] + 1;
+  } else {
+    if (tid < C) {
+      const float invstd = rsqrtf(rvar[tid] + eps);
+      const float s = gamma[tid] * invstd;
+      sc_s[tid] = s;
+      beta_s[tid] = beta[tid];
+      mean_s[tid] = rmean[tid];
+    }
+    __syncthreads();
+  }
+  const int e = blockIdx.x * NTHR + tid;
+  if (e >= total) return;
+  const int c = (e / (HO * WO)) % C;
+  const float sc = sc_s[c], bt = beta_s[c], mn = mean_s[c];
+  const int bc = e / (HO * WO), pix = e % (HO * WO);
+  const int ho = pix / WO, wo = pix % WO;
+  const T* src = y + (size_t)bc * H * W + (2 * ho) * W + 2 * wo;
+  float best = -1.f;
+  int bi = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float v = Cvt<T>::to_f(src[(k >> 1) * W + (k & 1)]);
+    const float z = fmaxf(rnd_t<T>((v - mn) * sc + bt), 0.f);
+    if (z > best) { best = z; bi = k; }
+  }
+  p[e] = Cvt<T>::from_f(best);
+  idx[e] = (uint8_t)bi;
+}
+
+// mean / invstd of channel c from the final stats buffer.
+template <int C>
+__device__ __forceinline__ void stats_mean_invstd(const float* fstats, int c, float eps, float& mean,
+                                                  float& invstd, float& n) {
+  n = fstats[2 * C];
+  const float m1 = fstats[c] / n;
+  mean = fstats[2 * C + 1 + c] + m1;
+  invstd = rsqrtf(fmaxf(fstats[C + c] / n - m1 * m1, 0.f) + eps);
+}
+
+// ---------------------------------------------------------------------------
+// Backward part 1: route the pooled grad through max-pool (argmax) and ReLU
+// (pooled output > 0), and reduce per channel into bslab[split][2C]:
+//   [c]     sum dy          (-> grad of BN bias)
+//   [C + c] sum dy * xhat   (-> grad of BN weight)
+// grid = (C, kBwdSplit over the batch).
+// ---------------------------------------------------------------------------
+template <typename T, int C, int H, int W>
+__global__ void __launch_bounds__(NTHR)
+bwd_reduce_kernel(const T* __restrict__ dp, const T* __restrict__ p, const uint8_t* __restrict__ idx,
+                  const T* __restrict__ y, const float* __restrict__ fstats, float eps,
+                  float* __restrict__ bslab, int B) {
+  constexpr int HO = H / 2, WO = W / 2, PP = HO * WO;
+  __shared__ float red[2 * NTHR / 64];
+  const int c = blockIdx.x;
+  const int nsplit = gridDim.y;
+  const int b0 = (B * blockIdx.y) / nsplit, b1 = (B * (blockIdx.y + 1)) / nsplit;
+  float mean, invstd, n;
+  stats_mean_invstd<C>(fstats, c, eps, mean, invstd, n);
+  float a1 = 0.f, a2 = 0.f;
+  const int cnt = (b1 - b0) * PP;
+  for (int t = threadIdx.x; t < cnt; t += NTHR) {
+    const int b = b0 + t / PP, pix = t % PP;
+    const size_t e = ((size_t)b * C + c) * PP + pix;
+    const float pv = Cvt<T>::to_f(p[e]);
+    if (pv > 0.f) {
+      const float g = Cvt<T>::to_f(dp[e]);
+      const int k = idx[e];
+      const int ho = pix / WO, wo = pix % WO;
+      const float yv = Cvt<T>::to_f(
+          y[((size_t)b * C + c) * H * W + (2 * ho + (k >> 1)) * W + 2 * wo + (k & 1)]);
+      a1 += g;
+      a2 += g * (yv - mean) * invstd;
+    }
+  }
+  a1 = wave_sum(a1);
+  a2 = wave_sum(a2);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) { red[wv] = a1; red[NTHR / 64 + wv] = a2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t1 = 0.f, t2 = 0.f;
+    for (int i = 0; i < NTHR / 64; ++i) { t1 += red[i]; t2 += red[NTHR / 64 + i]; }
+    bslab[blockIdx.y * 2 * C + c] = t1;
+    bslab[blockIdx.y * 2 * C + C + c] = t2;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Backward part 2: BN input gradient at full resolution, one thread per
+// pooled element (its 2x2 window):
+//   dx = gamma*invstd*(dy - S1/n - xhat*S2/n),  dy = routed pooled grad or 0
+// S1, S2 = column sums of the (all-reduced) bslab.
+// ---------------------------------------------------------------------------
+template <typename T, int C, int H, int W>
+__global__ void __launch_bounds__(NTHR)
+bwd_elemt_kernel(const T* __restrict__ dp, const T* __restrict__ p, const uint8_t* __restrict__ idx,
+                 const T* __restrict__ y, const float* __restrict__ fstats,
+                 const float* __restrict__ gslab, int nsplit, const float* __restrict__ gamma, float eps,
+                 T* __restrict__ dx, int total) {
+  constexpr int HO = H / 2, WO = W / 2, PP = HO * WO;
+  __shared__ float k_s[3 * C];
+  __shared__ float m_s[2 * C];
+  const int tid = threadIdx.x;
+  if (tid < C) {
+    float s1 = 0.f, s2 = 0.f;
+    for (int s = 0; s < nsplit; ++s) {
+      s1 += gslab[s * 2 * C + tid];
+      s2 += gslab[s * 2 * C + C + tid];
+    }
+    float mean, invstd, n;
+    stats_mean_invstd<C>(fstats, tid, eps, mean, invstd, n);
+    k_s[tid] = s1 / n;
+    k_s[C + tid] = s2 / n;
+    k_s[2 * C + tid] = gamma[tid] * invstd;
+    m_s[tid] = mean;
+    m_s[C + tid] = invstd;
+  }
+  __syncthreads();
+  const int e = blockIdx.x * NTHR + tid;
+  if (e >= total) return;
+  const int bc = e / PP, pix = e % PP;
+  const int c = bc % C;
+  const float k1 = k_s[c], k2 = k_s[C + c], gi = k_s[2 * C + c];
+  const float mean = m_s[c], invstd = m_s[C + c];
+  const float pv = Cvt<T>::to_f(p[e]);
+  const float g = pv > 0.f ? Cvt<T>::to_f(dp[e]) : 0.f;
+  const int kk = idx[e];
+  const int ho = pix / WO, wo = pix % WO;
+  const size_t base = (size_t)bc * H * W + (2 * ho) * W + 2 * wo;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const size_t o = base + (k >> 1) * W + (k & 1);
+    const float xh = (Cvt<T>::to_f(y[o]) - mean) * invstd;
+    const float dy = (k == kk) ? g : 0.f;
+    dx[o] = Cvt<T>::from_f(gi * (dy - k1 - xh * k2));
+  }
+}
+
+static __global__ void __launch_bounds__(NTHR)
+slab_reduce_kernel(const float* __restrict__ slab1, int rows1, int n1, float* __restrict__ out1,
+                   const float* __restrict__ slab2, int rows2, int n2, float* __restrict__ out2) {
+  slab_reduce_body(slab1, rows1, n1, out1, slab2, rows2, n2, out2, (int)blockIdx.x);
+}
 
 // ===========================================================================
 // Host side
@@ -29,15 +242,6 @@ static bool with_chw(int C, int H, int W, F&& f) {
   if (C == 16 && H == 28 && W == 28) { f(std::integral_constant<int, 0>{}); return true; }
   if (C == 32 && H == 14 && W == 14) { f(std::integral_constant<int, 1>{}); return true; }
   return false;
-}
-
-template <typename F>
-static void with_t(DT dt, F&& f) {
-  switch (dt) {
-    case DT::F32: f(float{}); break;
-    case DT::BF16: f(__hip_bfloat16{}); break;
-    case DT::F16: f(__half{}); break;
-  }
 }
 
 bool supported(int cin, int cout, int h, int w) {

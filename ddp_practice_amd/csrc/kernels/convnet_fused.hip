@@ -19,7 +19,8 @@
 // is deterministic (no float atomics).
 #include <type_traits>
 
-#include "convblock_impl.h"
+#include "conv5x5.h"
+#include "conv5x5_wgrad.h"
 #include "comm/xgmi.h"
 
 namespace dpa {
@@ -34,6 +35,7 @@ using cb::IDX_POS;
 using cb::IDX_RELU;
 using cb::Pair2;
 using cb::PoolIn;
+using cb::with_t;
 
 constexpr int HF = 256;        // head forward: one workgroup per image
 constexpr int NTHR_HB = 256;   // head backward: one workgroup per BN2 channel
@@ -198,15 +200,6 @@ head_bwd_kernel(const T* __restrict__ dlogits, const float* __restrict__ wfc, co
 // ===========================================================================
 // Host side
 // ===========================================================================
-template <typename F>
-static void with_t(DT dt, F&& f) {
-  switch (dt) {
-    case DT::F32: f(float{}); break;
-    case DT::BF16: f(__hip_bfloat16{}); break;
-    case DT::F16: f(__half{}); break;
-  }
-}
-
 static BNParams bn_params(c10::optional<at::Tensor> fslab, at::Tensor fstats, at::Tensor gamma, at::Tensor beta,
                           at::Tensor rmean, at::Tensor rvar, at::Tensor nbt, double momentum, double eps, bool train,
                           int C) {
@@ -257,7 +250,7 @@ static BwdIn<T> bwd_in(at::Tensor dp, at::Tensor idx, at::Tensor y, at::Tensor f
 typedef std::shared_ptr<xgmi::XgmiComm> XcPtr;
 static xgmi::XSite site_of(const XcPtr& xc, int s) { return xc ? xc->site(s) : xgmi::XSite{}; }
 
-// Workgroups per image of the conv2 forward: cb::kFwd2SplitT<T> (convblock_impl.h; the knobs
+// Workgroups per image of the conv2 forward: cb::kFwd2SplitT<T> (convblock_bn.h; the knobs
 // DPA_FWD2_SPLIT / DPA_FWD2_SPLIT_F32).  fp32, whose 16x16x4 MFMA chain per output tile is 4x
 // as long, runs 4 workgroups per image (fp32 step 0.0640 -> 0.0617 ms, profiles/r6m_split_ab.txt).
 // The consumers take the slab's row count from its size (nrows).
@@ -389,8 +382,18 @@ void head_bwd(at::Tensor dlogits, at::Tensor wfc, at::Tensor p2, at::Tensor idx2
   DPA_CHECK_LAUNCH();
 }
 
-// Layer-1 conv (+BN1 sums when training) that also packs the layer-2 weights
-// into their low-precision LDS tile layouts (cb::pack_w2).
+static void check_conv1_pack(const at::Tensor& x, const at::Tensor& w1, const at::Tensor& b1, const at::Tensor& y1,
+                             const at::Tensor& w2, const at::Tensor& wpk_f, const at::Tensor& wpk_d) {
+  const int64_t B = x.size(0);
+  TORCH_CHECK(x.size(1) == 1 && x.size(2) == 28 && x.size(3) == 28 && w1.numel() == 16 * 25 && b1.numel() == 16,
+              "fused conv1 expects the ConvNet shapes");
+  TORCH_CHECK(w2.numel() == 32 * 16 * 25 && w2.scalar_type() == at::kFloat && w1.scalar_type() == at::kFloat);
+  TORCH_CHECK(y1.numel() == (int64_t)B * 16 * 784 && y1.scalar_type() == x.scalar_type());
+  TORCH_CHECK(wpk_f.numel() == cb::W2F_LEN && wpk_d.numel() == cb::W2D_LEN &&
+              wpk_f.scalar_type() == x.scalar_type() && wpk_d.scalar_type() == x.scalar_type());
+}
+
+// Layer-1 conv (+BN1 sums when training) that also packs the layer-2 weights (cb::pack_w2).
 void conv1_fwd_pack(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor y1, c10::optional<at::Tensor> fslab1,
                     c10::optional<at::Tensor> fstats1, c10::optional<at::Tensor> shift1, at::Tensor w2,
                     at::Tensor wpk_f, at::Tensor wpk_d) {
@@ -398,12 +401,7 @@ void conv1_fwd_pack(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor y1, c
   DPA_CHECK_INPUT(wpk_f); DPA_CHECK_INPUT(wpk_d);
   const int B = (int)x.size(0);
   typedef cb::SH<0> S;
-  TORCH_CHECK(x.size(1) == 1 && x.size(2) == 28 && x.size(3) == 28 && w1.numel() == 16 * 25 && b1.numel() == 16,
-              "fused conv1 expects the ConvNet shapes");
-  TORCH_CHECK(w2.numel() == 32 * 16 * 25 && w2.scalar_type() == at::kFloat && w1.scalar_type() == at::kFloat);
-  TORCH_CHECK(y1.numel() == (int64_t)B * 16 * 784 && y1.scalar_type() == x.scalar_type());
-  TORCH_CHECK(wpk_f.numel() == cb::W2F_LEN && wpk_d.numel() == cb::W2D_LEN &&
-              wpk_f.scalar_type() == x.scalar_type() && wpk_d.scalar_type() == x.scalar_type());
+  check_conv1_pack(x, w1, b1, y1, w2, wpk_f, wpk_d);
   const bool st = fslab1.has_value();
   if (st)
     TORCH_CHECK(fslab1->numel() == (int64_t)B * S::SPLIT * cb::fslab_row(16) && fstats1->numel() == cb::stats_len(16) &&
@@ -437,17 +435,12 @@ void conv1_fwd_pack_gather(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tenso
   DPA_CHECK_INPUT(order); DPA_CHECK_INPUT(ctr); DPA_CHECK_INPUT(lab_out);
   const int B = (int)x.size(0);
   typedef cb::SH<0> S;
-  TORCH_CHECK(x.size(1) == 1 && x.size(2) == 28 && x.size(3) == 28 && w1.numel() == 16 * 25 && b1.numel() == 16,
-              "fused conv1 expects the ConvNet shapes");
   TORCH_CHECK(imgs.scalar_type() == at::kByte && imgs.dim() == 3 && imgs.size(1) == 28 && imgs.size(2) == 28,
               "gather: uint8 [N][28][28] dataset");
   TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == imgs.size(0));
   TORCH_CHECK(order.scalar_type() == at::kLong && ctr.scalar_type() == at::kInt && ctr.numel() >= 2);
   TORCH_CHECK(lab_out.scalar_type() == at::kLong && lab_out.numel() == B);
-  TORCH_CHECK(w2.numel() == 32 * 16 * 25 && w2.scalar_type() == at::kFloat && w1.scalar_type() == at::kFloat);
-  TORCH_CHECK(y1.numel() == (int64_t)B * 16 * 784 && y1.scalar_type() == x.scalar_type());
-  TORCH_CHECK(wpk_f.numel() == cb::W2F_LEN && wpk_d.numel() == cb::W2D_LEN &&
-              wpk_f.scalar_type() == x.scalar_type() && wpk_d.scalar_type() == x.scalar_type());
+  check_conv1_pack(x, w1, b1, y1, w2, wpk_f, wpk_d);
   TORCH_CHECK(fslab1.numel() == (int64_t)B * S::SPLIT * cb::fslab_row(16) && fstats1.numel() == cb::stats_len(16) &&
               shift1.numel() == 16);
   if (B == 0) return;
@@ -716,6 +709,8 @@ static bool lp_dyn_bwd() {
   }();
   return on;
 }
+template <typename T>  // whether the conv2 backward of T is the one dynamic-LDS launch
+static bool conv2_bwd_dyn() { return std::is_same<T, float>::value ? fp32_merged_bwd() : lp_dyn_bwd(); }
 
 // fp32 without the merged launch: the conv2 weight-gradient role and the fc weight gradient
 // in one launch (the data-gradient role's static LDS does not fit beside the weight gradient's)
@@ -817,13 +812,11 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
       bd.chk = fw.chk = grad_chk_of(chk, xc);
       bd.chk_coef = 1;
     }
-    if constexpr (std::is_same<T, float>::value) {
-      if (fp32_merged_bwd()) {  // one launch, the conv tiles in dynamic LDS (conv2_bwd_dyn_kernel)
-        hipLaunchKernelGGL(conv2_bwd_dyn_kernel<T>, dim3(ndg + nwg + nfc), dim3(cb::NTHR), conv2_bwd_dyn_bytes<T>(),
-                           cur_stream(), dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(),
-                           bw, ndg, nwg, fw);
-        return;
-      }
+    if (conv2_bwd_dyn<T>()) {  // one launch, the roles' tiles in dynamic LDS (the largest role's bytes)
+      hipLaunchKernelGGL(conv2_bwd_dyn_kernel<T>, dim3(ndg + nwg + nfc), dim3(cb::NTHR), conv2_bwd_dyn_bytes<T>(),
+                         cur_stream(), dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(),
+                         bw, ndg, nwg, fw);
+    } else if constexpr (std::is_same<T, float>::value) {
       // fp32 static tiles: the two roles' LDS (173 KB) exceed one CU's 160 KB -> separate launches
       // (the fc weight gradient: extra workgroups of the weight-gradient launch; its site's
       // tickets are the nwg conv workgroups', set above)
@@ -833,10 +826,6 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
                          kDgradSplitT<T>, PoolIn<T>{}, bd, ep, dptr<T>(wpk_d), cb::WPack<T>{});
       hipLaunchKernelGGL(conv2_wgrad_fc_kernel<T>, dim3(nwg + nfc), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(p1),
                          wslab2.data_ptr<float>(), bw, nwg, fw);
-    } else if (lp_dyn_bwd()) {  // the roles' tiles in dynamic LDS (the largest role's bytes)
-      hipLaunchKernelGGL(conv2_bwd_dyn_kernel<T>, dim3(ndg + nwg + nfc), dim3(cb::NTHR), conv2_bwd_dyn_bytes<T>(),
-                         cur_stream(), dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(),
-                         bw, ndg, nwg, fw);
     } else {
       hipLaunchKernelGGL(conv2_bwd_kernel<T>, dim3(ndg + nwg + nfc), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(wpk_d),
                          dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(), bw, ndg, nwg, fw);
@@ -959,17 +948,12 @@ bool sites_resident(int64_t B, at::ScalarType st) {
     ok = ok && co_resident(reinterpret_cast<const void*>(&head_fwd_kernel<T, 32, 14, 14, 16>), (int)B, HF, 0) &&
          co_resident(reinterpret_cast<const void*>(&head_fwd_kernel<T, 32, 14, 14, 64>), (int)B, HF, 0);
     chk(reinterpret_cast<const void*>(&cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<T>>), B * kDgradSplitT<T>);
-    if constexpr (!std::is_same<T, float>::value) {
-      if (lp_dyn_bwd())
-        ok = ok && co_resident(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<T>),
-                               (int)(B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS), cb::NTHR,
-                               conv2_bwd_dyn_bytes<T>());
-      else
-        chk(reinterpret_cast<const void*>(&conv2_bwd_kernel<T>), B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS);
-    } else if (fp32_merged_bwd())
+    if (conv2_bwd_dyn<T>())
       ok = ok && co_resident(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<T>),
                              (int)(B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS), cb::NTHR,
                              conv2_bwd_dyn_bytes<T>());
+    else if constexpr (!std::is_same<T, float>::value)
+      chk(reinterpret_cast<const void*>(&conv2_bwd_kernel<T>), B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS);
     chk(reinterpret_cast<const void*>(&conv2_wgrad_kernel<T>), wgrad2_wgs(B));
     chk(reinterpret_cast<const void*>(&cb::conv5x5_wgrad_kernel<T, 1, 16, 28, 28, WG1_ROWS, 2>),
         wgrad_bn_rows(1, B));

@@ -34,7 +34,7 @@
 #include <cstdlib>
 
 #include "comm/xgmi.h"
-#include "convblock_impl.h"
+#include "convblock_bn.h"
 
 namespace dpa {
 namespace cnh {

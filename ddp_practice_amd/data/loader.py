@@ -117,7 +117,7 @@ class DeviceLoader:
 
         ``defer=True`` (device counter only): launch nothing; the gather is recorded on
         ``images`` and performed by the first kernel of a model that consumes it
-        (the fused ConvNet's conv1, csrc/kernels/convblock_impl.h PRO 3).  Any other
+        (the fused ConvNet's conv1, csrc/kernels/conv5x5.h PRO 3).  Any other
         reader must call ``flush_pending(images)`` first; ``accepts_deferred`` says
         whether a model does it itself.
         """

@@ -1,4 +1,4 @@
-"""Row-window staging of the fused conv2 kernels (csrc/kernels/convblock_impl.h conv5x5_body WR):
+"""Row-window staging of the fused conv2 kernels (csrc/kernels/conv5x5.h conv5x5_body WR):
 a workgroup stages only the input rows its own output pixels read, and the pooled outputs are
 shared out by output pixel range.
 

@@ -1,4 +1,4 @@
-"""conv2 weight gradient decomposed by output slice (csrc/kernels/convblock_impl.h
+"""conv2 weight gradient decomposed by output slice (csrc/kernels/conv5x5_wgrad.h
 conv5x5_wgrad_body NSL, convnet_fused.hip conv2_wgrad_role): one slab row per image.
 
 Each row (dW partial | db partial of ONE image) and the column sums are compared with a
