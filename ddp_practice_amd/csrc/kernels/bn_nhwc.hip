@@ -4,14 +4,16 @@
 // contiguous.
 //
 // Geometry (every BN kernel): the channels are cut into column chunks of
-// CC = Lr*VEC <= 64 channels (8 lanes x 16 B bf16, 16 lanes fp32: 128 B of a row,
-// blockIdx.y = chunk); a lane owns one 16-B channel vector of its chunk for the
-// whole kernel (its per-channel coefficients live in registers) and walks rows
-// with stride RP = 256/Lr, U = 4 rows in flight per lane.
+// CC = Lr*VEC channels (blockIdx.y = chunk): at most CC_MAX = 64 in the statistics
+// kernels (8 lanes x 16 B bf16, 16 lanes fp32: 128 B of a row) and CC_ELT = 256 in
+// the elementwise ones (512 B of a row); a lane owns one 16-B channel vector of its
+// chunk for the whole kernel (its per-channel coefficients live in registers) and
+// walks rows with stride RP = 256/Lr (walk_rows), U = 4 rows in flight per lane
+// (UF = 8 in the forward statistics, which read one tensor).
 //
 //   forward (train)  stats:  per-channel sum(x - shift), sum((x - shift)^2);
 //                            per-workgroup partial rows, combined by a
-//                            two-level ticket tree (groups of 16 workgroups,
+//                            two-level ticket tree (groups of G1 = 128 workgroups,
 //                            then the groups) -> stats[2C+1] (+ shift copy);
 //                            the final reducer of chunk 0 bumps
 //                            num_batches_tracked.  SyncBN all-reduces the first
@@ -142,6 +144,31 @@ __device__ __forceinline__ void row_range(long long M, long long& r0, long long&
   r1 = r0 + per < M ? r0 + per : M;
 }
 
+// UU rows (stride RP, from row r) of the NIN tensors src[] in flight, then f(o, v) row by
+// row: o = element offset of the lane's vector, v[i] = its values in src[i] (f may overwrite)
+template <typename T, int UU, int NIN, typename F>
+__device__ __forceinline__ void row_pass(const Chunk<V16<T>::N>& g, int C, const T* const* src, long long r, F& f) {
+  float v[UU][NIN][V16<T>::N];
+#pragma unroll
+  for (int u = 0; u < UU; ++u) {
+    const long long o = (r + u * g.RP) * C + g.c0;
+#pragma unroll
+    for (int i = 0; i < NIN; ++i) load_vec<T>(src[i] + o, v[u][i]);
+  }
+#pragma unroll
+  for (int u = 0; u < UU; ++u) f((r + u * g.RP) * C + g.c0, v[u]);
+}
+
+// This (active) lane's rows of the row block: passes of UU rows, then the tail row by row.
+template <typename T, int UU, int NIN, typename F>
+__device__ __forceinline__ void walk_rows(const Chunk<V16<T>::N>& g, long long M, int C, const T* const* src, F&& f) {
+  long long r0, r1;
+  row_range(M, r0, r1);
+  long long r = r0 + g.ro;
+  for (; r + (UU - 1) * g.RP < r1; r += UU * g.RP) row_pass<T, UU, NIN>(g, C, src, r, f);
+  for (; r < r1; r += g.RP) row_pass<T, 1, NIN>(g, C, src, r, f);
+}
+
 // The statistics trees hand their partial rows over write-through (kernels/handoff.h:
 // st_wt / ld_wt, last_arriver); g_handoff_wt (bn_nhwc.set_handoff) = 0 restores the fenced
 // form (plain stores, release / acquire around the ticket).
@@ -194,7 +221,9 @@ __device__ __noinline__ void sum_rows(const float* __restrict__ src, int n, int 
 
 // Block partial -> part, then the two-level ticket tree of this chunk.  Returns
 // true in the single workgroup per chunk that ends with the chunk's W totals in
-// red[0, W).  part: [Gc*Gr + Gc*NG][W] floats; tickets: [Gc*NG + Gc].
+// red[0, W).  part: rows of W = 2 CC floats, the Gc*Gr block partials (chunk y's at y*Gr), then
+// the Gc*NG group sums (at y*NG): 2C*(Gr + NG) floats as Gc*W = 2C; tickets: Gc*NG group
+// counters, then one per chunk: Gc*(NG + 1) (check_workspace).
 // xs active (SyncBN): lane 0 of the chunk's finisher takes the site ticket into *tk before
 // the last level's loads (its round trip overlaps them).
 __device__ bool chunk_reduce(float* __restrict__ part, unsigned* __restrict__ tickets, int W, float* red,
@@ -278,6 +307,8 @@ fwd_stats_kernel(const T* __restrict__ x, long long M, int C, const float* __res
   float s1[VEC], s2[VEC], sh[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) s1[j] = s2[j] = sh[j] = 0.f;
+  // the walk stays written out: through walk_rows (UF = 8, one input) this kernel measured 14-23% slower
+  // at the ResNet-50 shapes (profiles/bn_nhwc_walker_ab.txt)
   long long r0, r1;
   row_range(M, r0, r1);
   if (g.active) {
@@ -325,95 +356,7 @@ fwd_stats_kernel(const T* __restrict__ x, long long M, int C, const float* __res
   }
 }
 
-// y = act((x - mean) * gamma*invstd + beta (+ res)) as fma(x, s, b) (+ res);
-// row block 0 of each chunk: running stats + save
-template <typename T, bool RES, bool RELU>
-__global__ void __launch_bounds__(THR)
-apply_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y, long long M, int C,
-             const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta,
-             float* __restrict__ rmean, float* __restrict__ rvar, const int64_t* __restrict__ nbt, float momentum,
-             float eps, int train, float* __restrict__ save) {
-  constexpr int VEC = V16<T>::N;
-  const Chunk<VEC> g(C);
-  if (!g.active) return;
-  float s[VEC], b[VEC], mean[VEC], istd[VEC], ga[VEC], be[VEC];
-  ldf<VEC>(gamma + g.c0, ga);
-  ldf<VEC>(beta + g.c0, be);
-  if (train) {
-    float s1[VEC], s2[VEC], sh[VEC], var[VEC];
-    ldf<VEC>(stats + g.c0, s1);
-    ldf<VEC>(stats + C + g.c0, s2);
-    ldf<VEC>(stats + 2 * C + SHIFT_OFF + g.c0, sh);
-    const float n = stats[2 * C];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      const float m1 = s1[j] / n;
-      var[j] = fmaxf(s2[j] / n - m1 * m1, 0.f);
-      mean[j] = sh[j] + m1;
-      istd[j] = rsqrtf(var[j] + eps);
-    }
-    if (blockIdx.x == 0 && g.ro == 0) {
-      stf<VEC>(save + g.c0, mean);
-      stf<VEC>(save + C + g.c0, istd);
-      const float mom = momentum >= 0.f ? momentum : 1.f / (float)nbt[0];  // nbt bumped by the stats kernel
-      float rm[VEC], rv[VEC];
-      ldf<VEC>(rmean + g.c0, rm);
-      ldf<VEC>(rvar + g.c0, rv);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        rm[j] = (1.f - mom) * rm[j] + mom * mean[j];
-        rv[j] = (1.f - mom) * rv[j] + mom * var[j] * (n / fmaxf(n - 1.f, 1.f));
-      }
-      stf<VEC>(rmean + g.c0, rm);
-      stf<VEC>(rvar + g.c0, rv);
-    }
-  } else {
-    float rv[VEC];
-    ldf<VEC>(rmean + g.c0, mean);
-    ldf<VEC>(rvar + g.c0, rv);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) istd[j] = rsqrtf(rv[j] + eps);
-  }
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    s[j] = ga[j] * istd[j];
-    b[j] = fmaf(-mean[j], s[j], be[j]);
-  }
-  long long r0, r1;
-  row_range(M, r0, r1);
-  auto row = [&](long long r, float* a, const float* rr) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float o = fmaf(a[j], s[j], b[j]);
-      if (RES) o += rr[j];
-      if (RELU) o = fmaxf(o, 0.f);
-      a[j] = o;
-    }
-    store_vec<T>(y + r * C + g.c0, a);
-  };
-  long long r = r0 + g.ro;
-  for (; r + (U - 1) * g.RP < r1; r += U * g.RP) {
-    float a[U][VEC], q[U][VEC];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      load_vec<T>(x + (r + u * g.RP) * C + g.c0, a[u]);
-      if (RES) load_vec<T>(res + (r + u * g.RP) * C + g.c0, q[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) row(r + u * g.RP, a[u], q[u]);
-  }
-  for (; r < r1; r += g.RP) {
-    float a[VEC], q[VEC];
-    load_vec<T>(x + r * C + g.c0, a);
-    if (RES) load_vec<T>(res + r * C + g.c0, q);
-    row(r, a, q);
-  }
-}
-
-// A projection bottleneck's tail in one pass: y = relu(bn(x) + bn_r(res)) -- the
-// downsample conv's BatchNorm applied while reading its raw output (apply_kernel would
-// first write the normalised identity and read it back: one pass of 2 tensors less).
-// Both BNs' coefficients, running stats and saves are handled as in apply_kernel.
+// One BatchNorm's arguments of the apply kernels (make_bnco on the host)
 struct BnCo {
   const float* stats;
   const float* gamma;
@@ -425,6 +368,9 @@ struct BnCo {
   float* save;
 };
 
+// This lane's coefficients of y = fma(x, s, b): s = gamma*invstd, b = beta - mean*s, from the
+// batch statistics (train) or the running ones; the leader lane of each channel vector saves
+// mean / invstd and updates the running statistics (momentum, unbiased variance).
 template <int VEC>
 __device__ __forceinline__ void bn_coef(const BnCo& p, int c0, int C, int train, bool leader, float* s, float* b) {
   float mean[VEC], istd[VEC], ga[VEC], be[VEC];
@@ -444,16 +390,18 @@ __device__ __forceinline__ void bn_coef(const BnCo& p, int c0, int C, int train,
       istd[j] = rsqrtf(var[j] + p.eps);
     }
     if (leader) {
+      const float mom = p.momentum >= 0.f ? p.momentum : 1.f / (float)p.nbt[0];  // nbt bumped by the stats kernel
       stf<VEC>(p.save + c0, mean);
       stf<VEC>(p.save + C + c0, istd);
-      const float mom = p.momentum >= 0.f ? p.momentum : 1.f / (float)p.nbt[0];
       float rm[VEC], rv[VEC];
       ldf<VEC>(p.rmean + c0, rm);
       ldf<VEC>(p.rvar + c0, rv);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
-        rm[j] = (1.f - mom) * rm[j] + mom * mean[j];
-        rv[j] = (1.f - mom) * rv[j] + mom * var[j] * (n / fmaxf(n - 1.f, 1.f));
+        // (1 - mom) * old + mom * new, the fma spelled out: left to the compiler, the two kernels
+        // that inline this fused different products and rounded differently
+        rm[j] = fmaf(1.f - mom, rm[j], mom * mean[j]);
+        rv[j] = fmaf(1.f - mom, rv[j], mom * var[j] * (n / fmaxf(n - 1.f, 1.f)));
       }
       stf<VEC>(p.rmean + c0, rm);
       stf<VEC>(p.rvar + c0, rv);
@@ -472,6 +420,35 @@ __device__ __forceinline__ void bn_coef(const BnCo& p, int c0, int C, int train,
   }
 }
 
+// y = act((x - mean) * gamma*invstd + beta (+ res)) as fma(x, s, b) (+ res);
+// row block 0 of each chunk: running stats + save
+template <typename T, bool RES, bool RELU>
+__global__ void __launch_bounds__(THR)
+apply_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y, long long M, int C, BnCo p,
+             int train) {
+  constexpr int VEC = V16<T>::N;
+  const Chunk<VEC> g(C);
+  if (!g.active) return;
+  float s[VEC], b[VEC];
+  bn_coef<VEC>(p, g.c0, C, train, blockIdx.x == 0 && g.ro == 0, s, b);
+  const T* src[2] = {x, res};
+  walk_rows<T, U, RES ? 2 : 1>(g, M, C, src, [&](long long o, float (*v)[VEC]) {
+    float* a = v[0];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      float t = fmaf(a[j], s[j], b[j]);
+      if (RES) t += v[RES ? 1 : 0][j];
+      if (RELU) t = fmaxf(t, 0.f);
+      a[j] = t;
+    }
+    store_vec<T>(y + o, a);
+  });
+}
+
+// A projection bottleneck's tail in one pass: y = relu(bn(x) + bn_r(res)) -- the
+// downsample conv's BatchNorm applied while reading its raw output (apply_kernel would
+// first write the normalised identity and read it back: one pass of 2 tensors less).
+// Both BNs' coefficients, running stats and saves are handled as in apply_kernel.
 template <typename T>
 __global__ void __launch_bounds__(THR)
 apply_resbn_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y, long long M, int C,
@@ -483,30 +460,13 @@ apply_resbn_kernel(const T* __restrict__ x, const T* __restrict__ res, T* __rest
   const bool leader = blockIdx.x == 0 && g.ro == 0;
   bn_coef<VEC>(m, g.c0, C, train, leader, s, b);
   bn_coef<VEC>(r, g.c0, C, train, leader, rs, rb);
-  long long r0, r1;
-  row_range(M, r0, r1);
-  auto row = [&](long long rr, float* a, const float* q) {
+  const T* src[2] = {x, res};
+  walk_rows<T, U, 2>(g, M, C, src, [&](long long o, float (*v)[VEC]) {
+    float *a = v[0], *q = v[1];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) a[j] = fmaxf(fmaf(a[j], s[j], b[j]) + fmaf(q[j], rs[j], rb[j]), 0.f);
-    store_vec<T>(y + rr * C + g.c0, a);
-  };
-  long long rr = r0 + g.ro;
-  for (; rr + (U - 1) * g.RP < r1; rr += U * g.RP) {
-    float a[U][VEC], q[U][VEC];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      load_vec<T>(x + (rr + u * g.RP) * C + g.c0, a[u]);
-      load_vec<T>(res + (rr + u * g.RP) * C + g.c0, q[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) row(rr + u * g.RP, a[u], q[u]);
-  }
-  for (; rr < r1; rr += g.RP) {
-    float a[VEC], q[VEC];
-    load_vec<T>(x + rr * C + g.c0, a);
-    load_vec<T>(res + rr * C + g.c0, q);
-    row(rr, a, q);
-  }
+    store_vec<T>(y + o, a);
+  });
 }
 
 // ReLU-derivative source of the backward kernels
@@ -553,40 +513,20 @@ bwd_stats_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T* __r
   float s1[VEC], s2[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) s1[j] = s2[j] = 0.f;
-  long long r0, r1;
-  row_range(M, r0, r1);
   if (g.active) {
     BwdLane<VEC, ACT> L;
     L.init(g.c0, C, save, gamma, beta);
-    auto acc = [&](const float* d, const float* xv, const float* yv) {
+    constexpr int NIN = ACT == ACT_Y ? 3 : 2;  // y is read only for its sign
+    const T* src[3] = {dy, x, y};
+    walk_rows<T, U, NIN>(g, M, C, src, [&](long long, float (*v)[VEC]) {
+      const float *d = v[0], *xv = v[1], *yv = v[NIN - 1];
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         const float z = L.dz(j, d[j], xv[j], yv[j]);
         s1[j] += z;
         s2[j] = fmaf(z, (xv[j] - L.mu[j]) * L.is[j], s2[j]);
       }
-    };
-    long long r = r0 + g.ro;
-    for (; r + (U - 1) * g.RP < r1; r += U * g.RP) {
-      float d[U][VEC], xv[U][VEC], yv[U][VEC];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long long o = (r + u * g.RP) * C + g.c0;
-        load_vec<T>(dy + o, d[u]);
-        load_vec<T>(x + o, xv[u]);
-        if (ACT == ACT_Y) load_vec<T>(y + o, yv[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc(d[u], xv[u], yv[u]);
-    }
-    for (; r < r1; r += g.RP) {
-      float d[VEC], xv[VEC], yv[VEC];
-      const long long o = r * C + g.c0;
-      load_vec<T>(dy + o, d);
-      load_vec<T>(x + o, xv);
-      if (ACT == ACT_Y) load_vec<T>(y + o, yv);
-      acc(d, xv, yv);
-    }
+    });
   }
   block_combine<VEC>(g, s1, s2, red, scratch);
   unsigned long long tk = 0;
@@ -604,6 +544,8 @@ bwd_stats_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T* __r
 }
 
 // dx = gamma*invstd*(dz - S1/n - xhat*S2/n); dres = dz
+// The row walk stays written out here: through walk_rows <float, ACT_NONE, true> takes 66 VGPRs
+// instead of 64 (7 waves per SIMD, not 8; profiles/bn_nhwc_walker_resources.txt).
 template <typename T, int ACT, bool DRES>
 __global__ void __launch_bounds__(THR)
 bwd_elemt_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T* __restrict__ x, long long M, int C,
@@ -698,7 +640,9 @@ bwd_elemt_rbn_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T*
       k1[j] /= n;
       k2[j] /= n;
     }
-    auto row = [&](long long o, const float* d, const float* xv, const float* yv, const float* rv) {
+    const T* src[4] = {dy, x, y, r};
+    walk_rows<T, U, 4>(g, M, C, src, [&](long long o, float (*v)[VEC]) {
+      const float *d = v[0], *xv = v[1], *yv = v[2], *rv = v[3];
       float z[VEC], e[VEC];
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
@@ -715,32 +659,7 @@ bwd_elemt_rbn_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T*
         s1[j] += z[j];
         s2[j] = fmaf(z[j], (rv[j] - rmu[j]) * ris[j], s2[j]);
       }
-    };
-    long long r0, r1;
-    row_range(M, r0, r1);
-    long long rr = r0 + g.ro;
-    for (; rr + (U - 1) * g.RP < r1; rr += U * g.RP) {
-      float d[U][VEC], xv[U][VEC], yv[U][VEC], rv[U][VEC];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long long o = (rr + u * g.RP) * C + g.c0;
-        load_vec<T>(dy + o, d[u]);
-        load_vec<T>(x + o, xv[u]);
-        load_vec<T>(y + o, yv[u]);
-        load_vec<T>(r + o, rv[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) row((rr + u * g.RP) * C + g.c0, d[u], xv[u], yv[u], rv[u]);
-    }
-    for (; rr < r1; rr += g.RP) {
-      float d[VEC], xv[VEC], yv[VEC], rv[VEC];
-      const long long o = rr * C + g.c0;
-      load_vec<T>(dy + o, d);
-      load_vec<T>(x + o, xv);
-      load_vec<T>(y + o, yv);
-      load_vec<T>(r + o, rv);
-      row(o, d, xv, yv, rv);
-    }
+    });
   }
   block_combine<VEC>(g, s1, s2, red, scratch);
   if (!chunk_reduce(part, tickets, 2 * g.CC, red, scratch, &s_flag, wt)) return;
@@ -937,17 +856,45 @@ static Grid2 chunk_grid(long long M, int C, int target, int cc = CC_MAX) {
 template <typename T>
 static Grid2 stats_grid(long long M, int C) {
   const int target = g_stats_target > 0 ? g_stats_target : (M * C * (long long)sizeof(T) < (64ll << 20) ? 128 : 256);
-  Grid2 g = chunk_grid<T>(M, C, target);
-  g.Gr = std::min(g.Gr, MAXGR);
-  return g;
+  return chunk_grid<T>(M, C, target);
 }
 static int elt_grid(long long nvec) {
   return (int)std::max<long long>(1, std::min<long long>((nvec + THR - 1) / THR, 4096));
 }
-static void check_workspace(const Grid2& g, int C, const at::Tensor& part, const at::Tensor& tickets) {
+// The grid of a kernel that ends in chunk_reduce: at most MAXGR row blocks, and a workspace that holds its tree
+static Grid2 stats_launch_checks(Grid2 g, int C, const at::Tensor& part, const at::Tensor& tickets) {
+  g.Gr = std::min(g.Gr, MAXGR);
   const int NG = (g.Gr + G1 - 1) / G1;
   TORCH_CHECK(part.numel() >= (long long)2 * C * (g.Gr + NG), "bn_nhwc: partial-sum workspace too small");
   TORCH_CHECK(tickets.numel() >= g.Gc * (NG + 1) && tickets.scalar_type() == at::kInt, "bn_nhwc: ticket workspace");
+  return g;
+}
+
+// runtime (act), (bool) -> std::integral_constant, so that every entry point has one launch site
+template <typename F>
+static void with_act(int64_t act, F&& f) {
+  switch (act) {
+    case ACT_Y: f(std::integral_constant<int, ACT_Y>{}); break;
+    case ACT_RECOMPUTE: f(std::integral_constant<int, ACT_RECOMPUTE>{}); break;
+    case ACT_NONE: f(std::integral_constant<int, ACT_NONE>{}); break;
+    default: TORCH_CHECK(false, "bn_nhwc: act must be 0, 1 or 2");
+  }
+}
+template <typename F>
+static void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+// One BatchNorm's arguments of the apply kernels.  stats is read only in training, save written only there.
+static BnCo make_bnco(int64_t C, bool train, const at::Tensor& stats, const at::Tensor& gamma, const at::Tensor& beta,
+                      const at::Tensor& rmean, const at::Tensor& rvar, const at::Tensor& nbt, double momentum,
+                      double eps, const at::Tensor& save) {
+  for (const at::Tensor* t : {&stats, &gamma, &beta, &rmean, &rvar, &save})
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous(), "bn_nhwc: fp32 contiguous BN tensors");
+  TORCH_CHECK(save.numel() >= 2 * C && gamma.numel() == C, "bn_nhwc: BN tensor sizes");
+  if (train) TORCH_CHECK(stats.numel() >= 3 * C + SHIFT_OFF, "bn_nhwc: statistics tensor too small");
+  return {stats.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(), rmean.data_ptr<float>(),
+          rvar.data_ptr<float>(), nbt.data_ptr<int64_t>(), (float)momentum, (float)eps, save.data_ptr<float>()};
 }
 
 // part: >= 2C*(MAXGR + MAXGR/G1) floats; tickets: >= MAXTICKETS zero-initialised int32 (re-armed by the kernels)
@@ -967,8 +914,7 @@ void fwd_stats(at::Tensor x, int64_t C, at::Tensor shift, at::Tensor part, at::T
   TORCH_CHECK(stats.numel() >= 3 * C + SHIFT_OFF && shift.numel() == C);
   dispatch(x, [&](auto tag) {
     typedef decltype(tag) T;
-    const Grid2 g = stats_grid<T>(M, (int)C);
-    check_workspace(g, (int)C, part, ticket);
+    const Grid2 g = stats_launch_checks(stats_grid<T>(M, (int)C), (int)C, part, ticket);
     hipLaunchKernelGGL(fwd_stats_kernel<T>, dim3(g.Gr, g.Gc), dim3(THR), 0, cur_stream(), dp<T>(x), M, (int)C,
                        shift.data_ptr<float>(), part.data_ptr<float>(),
                        reinterpret_cast<unsigned*>(ticket.data_ptr<int>()), stats.data_ptr<float>(),
@@ -984,21 +930,17 @@ void apply(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor y, int64_t C,
   check_rows(x, M, (int)C);
   check_rows(y, M, (int)C);
   if (res.has_value()) check_rows(*res, M, (int)C);
+  const BnCo p = make_bnco(C, train, stats, gamma, beta, rmean, rvar, nbt, momentum, eps, save);
   dispatch(x, [&](auto tag) {
     typedef decltype(tag) T;
     const Grid2 g = chunk_grid<T>(M, (int)C, g_apply_target, CC_ELT);
-    auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(g.Gr, g.Gc), dim3(THR), 0, cur_stream(), dp<T>(x),
-                         res.has_value() ? dp<T>(*res) : nullptr, dp<T>(y), M, (int)C, stats.data_ptr<float>(),
-                         gamma.data_ptr<float>(), beta.data_ptr<float>(), rmean.data_ptr<float>(),
-                         rvar.data_ptr<float>(), nbt.data_ptr<int64_t>(), (float)momentum, (float)eps, (int)train,
-                         save.data_ptr<float>());
-    };
-    if (res.has_value()) {
-      if (relu) go(apply_kernel<T, true, true>); else go(apply_kernel<T, true, false>);
-    } else {
-      if (relu) go(apply_kernel<T, false, true>); else go(apply_kernel<T, false, false>);
-    }
+    with_bool(res.has_value(), [&](auto RES) {
+      with_bool(relu, [&](auto RELU) {
+        auto kern = apply_kernel<T, decltype(RES)::value, decltype(RELU)::value>;
+        hipLaunchKernelGGL(kern, dim3(g.Gr, g.Gc), dim3(THR), 0, cur_stream(), dp<T>(x),
+                           res.has_value() ? dp<T>(*res) : nullptr, dp<T>(y), M, (int)C, p, (int)train);
+      });
+    });
   });
   DPA_CHECK_LAUNCH();
 }
@@ -1013,17 +955,8 @@ void apply_resbn(at::Tensor x, at::Tensor res, at::Tensor y, int64_t C, at::Tens
   check_rows(res, M, (int)C);
   check_rows(y, M, (int)C);
   TORCH_CHECK(x.scalar_type() == res.scalar_type() && x.scalar_type() == y.scalar_type(), "apply_resbn: one dtype");
-  for (const at::Tensor* t : {&stats, &gamma, &beta, &rmean, &rvar, &save, &rstats, &rgamma, &rbeta, &rrmean, &rrvar,
-                              &rsave})
-    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous(), "apply_resbn: fp32 contiguous BN tensors");
-  TORCH_CHECK(save.numel() >= 2 * C && rsave.numel() >= 2 * C && gamma.numel() == C && rgamma.numel() == C,
-              "apply_resbn: sizes");
-  if (train)
-    TORCH_CHECK(stats.numel() >= 3 * C + SHIFT_OFF && rstats.numel() >= 3 * C + SHIFT_OFF, "apply_resbn: stats");
-  BnCo m{stats.data_ptr<float>(), gamma.data_ptr<float>(), beta.data_ptr<float>(), rmean.data_ptr<float>(),
-         rvar.data_ptr<float>(), nbt.data_ptr<int64_t>(), (float)momentum, (float)eps, save.data_ptr<float>()};
-  BnCo r{rstats.data_ptr<float>(), rgamma.data_ptr<float>(), rbeta.data_ptr<float>(), rrmean.data_ptr<float>(),
-         rrvar.data_ptr<float>(), rnbt.data_ptr<int64_t>(), (float)rmomentum, (float)reps, rsave.data_ptr<float>()};
+  const BnCo m = make_bnco(C, train, stats, gamma, beta, rmean, rvar, nbt, momentum, eps, save);
+  const BnCo r = make_bnco(C, train, rstats, rgamma, rbeta, rrmean, rrvar, rnbt, rmomentum, reps, rsave);
   dispatch(x, [&](auto tag) {
     typedef decltype(tag) T;
     const Grid2 g = chunk_grid<T>(M, (int)C, g_apply_target, CC_ELT);
@@ -1045,18 +978,15 @@ void bwd_stats(at::Tensor dy, c10::optional<at::Tensor> y, at::Tensor x, int64_t
   TORCH_CHECK(out.numel() >= 2 * C && save.numel() >= 2 * C);
   dispatch(x, [&](auto tag) {
     typedef decltype(tag) T;
-    const Grid2 g = stats_grid<T>(M, (int)C);
-    check_workspace(g, (int)C, part, ticket);
-    auto go = [&](auto kern) {
+    const Grid2 g = stats_launch_checks(stats_grid<T>(M, (int)C), (int)C, part, ticket);
+    with_act(act, [&](auto ACT) {
+      auto kern = bwd_stats_kernel<T, decltype(ACT)::value>;
       hipLaunchKernelGGL(kern, dim3(g.Gr, g.Gc), dim3(THR), 0, cur_stream(), dp<T>(dy),
                          act == ACT_Y ? dp<T>(*y) : nullptr, dp<T>(x), M, (int)C, save.data_ptr<float>(),
                          gamma.data_ptr<float>(), beta.data_ptr<float>(), part.data_ptr<float>(),
                          reinterpret_cast<unsigned*>(ticket.data_ptr<int>()), out.data_ptr<float>(),
                          dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), g_handoff_wt, stats_site(xc, C, g.Gc));
-    };
-    if (act == ACT_Y) go(bwd_stats_kernel<T, ACT_Y>);
-    else if (act == ACT_RECOMPUTE) go(bwd_stats_kernel<T, ACT_RECOMPUTE>);
-    else go(bwd_stats_kernel<T, ACT_NONE>);
+    });
   });
   DPA_CHECK_LAUNCH();
 }
@@ -1074,16 +1004,15 @@ void bwd_elemt(at::Tensor dy, c10::optional<at::Tensor> y, at::Tensor x, int64_t
   dispatch(x, [&](auto tag) {
     typedef decltype(tag) T;
     const Grid2 g = chunk_grid<T>(M, (int)C, g_elemt_target, CC_ELT);
-    auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(g.Gr, g.Gc), dim3(THR), 0, cur_stream(), dp<T>(dy),
-                         act == ACT_Y ? dp<T>(*y) : nullptr, dp<T>(x), M, (int)C, save.data_ptr<float>(),
-                         sums.data_ptr<float>(), fstats.data_ptr<float>(), gamma.data_ptr<float>(),
-                         beta.data_ptr<float>(), dp<T>(dx), dres.has_value() ? dp<T>(*dres) : nullptr);
-    };
-    const bool d = dres.has_value();
-    if (act == ACT_Y) { if (d) go(bwd_elemt_kernel<T, ACT_Y, true>); else go(bwd_elemt_kernel<T, ACT_Y, false>); }
-    else if (act == ACT_RECOMPUTE) { if (d) go(bwd_elemt_kernel<T, ACT_RECOMPUTE, true>); else go(bwd_elemt_kernel<T, ACT_RECOMPUTE, false>); }
-    else { if (d) go(bwd_elemt_kernel<T, ACT_NONE, true>); else go(bwd_elemt_kernel<T, ACT_NONE, false>); }
+    with_act(act, [&](auto ACT) {
+      with_bool(dres.has_value(), [&](auto DRES) {
+        auto kern = bwd_elemt_kernel<T, decltype(ACT)::value, decltype(DRES)::value>;
+        hipLaunchKernelGGL(kern, dim3(g.Gr, g.Gc), dim3(THR), 0, cur_stream(), dp<T>(dy),
+                           act == ACT_Y ? dp<T>(*y) : nullptr, dp<T>(x), M, (int)C, save.data_ptr<float>(),
+                           sums.data_ptr<float>(), fstats.data_ptr<float>(), gamma.data_ptr<float>(),
+                           beta.data_ptr<float>(), dp<T>(dx), dres.has_value() ? dp<T>(*dres) : nullptr);
+      });
+    });
   });
   DPA_CHECK_LAUNCH();
 }
@@ -1099,9 +1028,7 @@ void bwd_elemt_rbn(at::Tensor dy, at::Tensor y, at::Tensor x, int64_t C, at::Ten
               "bwd_elemt_rbn: sizes");
   dispatch(x, [&](auto tag) {
     typedef decltype(tag) T;
-    Grid2 g = chunk_grid<T>(M, (int)C, g_elemt_target, CC_ELT);
-    g.Gr = std::min(g.Gr, MAXGR);
-    check_workspace(g, (int)C, part, ticket);
+    const Grid2 g = stats_launch_checks(chunk_grid<T>(M, (int)C, g_elemt_target, CC_ELT), (int)C, part, ticket);
     hipLaunchKernelGGL(bwd_elemt_rbn_kernel<T>, dim3(g.Gr, g.Gc), dim3(THR), 0, cur_stream(), dp<T>(dy), dp<T>(y),
                        dp<T>(x), M, (int)C, save.data_ptr<float>(), sums.data_ptr<float>(), fstats.data_ptr<float>(),
                        gamma.data_ptr<float>(), beta.data_ptr<float>(), dp<T>(dx), dp<T>(dres), dp<T>(r),

@@ -149,6 +149,39 @@ class BNTap:
         self.save = self.weight = self.bias = self.sums = self.xc = None
 
 
+def _batch_stats(K, x, C, running_mean, nbt, pre, xc, ws=None):
+    """The forward statistics tensor of ``x``: ``pre`` when the producing conv's epilogue already
+    computed it (ops/conv_igemm.py), else one fwd_stats launch (``ws``: the workspace, fetched
+    when None).  The SyncBN all-reduce (no site exchange, ``xc`` None) is the caller's."""
+    if pre is not None:
+        return pre
+    part, ticket = ws if ws is not None else _Workspace.get(x.device, C)
+    stats = torch.empty(3 * C + 4, dtype=torch.float32, device=x.device)
+    K.fwd_stats(x, C, running_mean, part, ticket, stats, nbt, xc=xc)
+    return stats
+
+
+def _backward_sums(ctx, K, dy, y, x, act, save, weight, bias):
+    """(sums, dgamma, dbeta) of a training BN's backward: the sums its tap holds for this ``dy``
+    (taken by the consumer conv's data-gradient epilogue) or one bwd_stats launch; the tap is
+    cleared; ``sums`` all-reduced unless the finishers exchanged them (ctx.xc)."""
+    C = x.shape[1]
+    f32 = dict(dtype=torch.float32, device=x.device)
+    bt = getattr(ctx, "btap", None)
+    if bt is not None and bt.matches(dy):
+        out, dgamma, dbeta = bt.sums
+    else:
+        part, ticket = _Workspace.get(x.device, C)
+        out, dgamma, dbeta = torch.empty(2 * C, **f32), torch.empty(C, **f32), torch.empty(C, **f32)
+        K.bwd_stats(dy, y, x, C, act, save, weight, bias, part, ticket, out, dgamma, dbeta, xc=ctx.xc)
+    if bt is not None:
+        bt.clear()
+        ctx.btap = None
+    # out is already global when the finishers exchanged it (ctx.xc)
+    sums = ctx.comm.all_reduce(out) if (ctx.sync and ctx.xc is None) else out
+    return sums, dgamma, dbeta
+
+
 class BNActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, res, running_mean, running_var, nbt, momentum, eps, training, relu, comm,
@@ -164,12 +197,7 @@ class BNActFn(torch.autograd.Function):
         if training:
             sync = comm is not None and comm.active
             xc = sync_site(comm)  # SyncBN inside the statistics finishers (also the producing conv's)
-            if pre is not None:  # computed in the producing conv's epilogue (ops/conv_igemm.py)
-                stats = pre
-            else:
-                part, ticket = _Workspace.get(dev, C)
-                stats = torch.empty(3 * C + 4, **f32)
-                K.fwd_stats(x, C, running_mean, part, ticket, stats, nbt, xc=xc)
+            stats = _batch_stats(K, x, C, running_mean, nbt, pre, xc)
             if sync and xc is None:
                 comm.all_reduce_(stats.narrow(0, 0, 2 * C + 1))
             save = torch.empty(2 * C, **f32)
@@ -198,21 +226,7 @@ class BNActFn(torch.autograd.Function):
         x, y, weight, bias, save, stats = ctx.saved_tensors
         C = x.shape[1]
         dy = _cl(dy)
-        f32 = dict(dtype=torch.float32, device=x.device)
-        bt = getattr(ctx, "btap", None)
-        if bt is not None and bt.matches(dy):
-            out, dgamma, dbeta = bt.sums  # taken by the consumer conv's data-gradient epilogue
-        else:
-            part, ticket = _Workspace.get(x.device, C)
-            out = torch.empty(2 * C, **f32)
-            dgamma = torch.empty(C, **f32)
-            dbeta = torch.empty(C, **f32)
-            K.bwd_stats(dy, y, x, C, ctx.act, save, weight, bias, part, ticket, out, dgamma, dbeta, xc=ctx.xc)
-        if bt is not None:
-            bt.clear()
-            ctx.btap = None
-        # out is already global when the finishers exchanged it (ctx.xc)
-        sums = ctx.comm.all_reduce(out) if (ctx.sync and ctx.xc is None) else out
+        sums, dgamma, dbeta = _backward_sums(ctx, K, dy, y, x, ctx.act, save, weight, bias)
         dx = torch.empty_like(x, memory_format=_CL)
         dres = torch.empty_like(x, memory_format=_CL) if ctx.has_res else None
         K.bwd_elemt(dy, y, x, C, ctx.act, save, sums, stats, weight, bias, dx, dres)
@@ -256,16 +270,11 @@ class BNResBNFn(torch.autograd.Function):
         stats = rstats = None
         xc = None
         if training:
-            stats, rstats = pre, rpre
             sync = comm is not None and comm.active
             xc = sync_site(comm)
-            part, ticket = _Workspace.get(dev, C)
-            if stats is None:
-                stats = torch.empty(3 * C + 4, **f32)
-                K.fwd_stats(x, C, bn.running_mean, part, ticket, stats, bn.num_batches_tracked, xc=xc)
-            if rstats is None:
-                rstats = torch.empty(3 * C + 4, **f32)
-                K.fwd_stats(r, C, rbn.running_mean, part, ticket, rstats, rbn.num_batches_tracked, xc=xc)
+            ws = _Workspace.get(dev, C)
+            stats = _batch_stats(K, x, C, bn.running_mean, bn.num_batches_tracked, pre, xc, ws)
+            rstats = _batch_stats(K, r, C, rbn.running_mean, rbn.num_batches_tracked, rpre, xc, ws)
             if sync and xc is None:
                 comm.all_reduce_(stats.narrow(0, 0, 2 * C + 1))
                 comm.all_reduce_(rstats.narrow(0, 0, 2 * C + 1))
@@ -297,16 +306,7 @@ class BNResBNFn(torch.autograd.Function):
         dy = _cl(dy)
         f32 = dict(dtype=torch.float32, device=x.device)
         part, ticket = _Workspace.get(x.device, C)
-        bt = ctx.btap
-        if bt is not None and bt.matches(dy):
-            out, dgamma, dbeta = bt.sums
-        else:
-            out, dgamma, dbeta = torch.empty(2 * C, **f32), torch.empty(C, **f32), torch.empty(C, **f32)
-            K.bwd_stats(dy, y, x, C, 1, save, weight, bias, part, ticket, out, dgamma, dbeta, xc=ctx.xc)
-        if bt is not None:
-            bt.clear()
-            ctx.btap = None
-        sums = ctx.comm.all_reduce(out) if (ctx.sync and ctx.xc is None) else out
+        sums, dgamma, dbeta = _backward_sums(ctx, K, dy, y, x, 1, save, weight, bias)
         dx = torch.empty_like(x, memory_format=_CL)
         dz = torch.empty_like(x, memory_format=_CL)
         # bn's elementwise backward, which also takes the downsample BN's sums of dz

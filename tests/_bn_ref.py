@@ -38,6 +38,40 @@ ELEM_C = (8, 24, 72, 320)
 ELEM_C_BIG = 2048  # one bf16 case
 
 
+# "one row block" cases of section (b): ELEM_ROWS[0] rows under set_grid_targets(1, 1, 1), where
+# every active lane walks at least one full pass of U rows and some lane a tail row as well
+# (tests/test_bn_nhwc_ref_cpu.py checks that from geom; one exception, below)
+ONE_BLOCK_CASES = ((torch.float32, 72), (torch.bfloat16, 72), (torch.float16, 24), (torch.bfloat16, 320))
+# (fp16, 24) is one chunk of 3 lanes per row, RP = 85: 189 rows are 2-3 rows per lane, tail rows
+# only.  It runs (a row block of tails alone), and fp16 gets its pass + tail from C = 72.
+ONE_BLOCK_TAIL_ONLY = ((torch.float16, 24),)
+ONE_BLOCK_EXTRA = ((torch.float16, 72),)
+STATS_ONE_BLOCK = (torch.float32, 64, 189)  # (dtype, C, M) with a pass and a tail row in the statistics kernels
+THR, U, UF, MAXGR = 256, 4, 8, 1024  # csrc/kernels/bn_nhwc.hip
+
+
+def geom(M, ch, target, dtype, cc=64):
+    """(row blocks, channel chunks, rows per pass RP, rows per row block, active lanes) of
+    chunk_grid / Chunk / row_range (cc 64: the statistics kernels; 256: the elementwise ones)."""
+    vec = VEC[dtype]
+    while cc > vec and not (ch <= cc or ch % cc == 0):
+        cc //= 2
+    ccw = ch if ch <= cc else cc
+    lr = ccw // vec
+    rp, gc = THR // lr, ch // ccw
+    gr = min(max(1, -(-M // (rp * U))), max(1, -(-target // gc)), MAXGR)
+    return gr, gc, rp, -(-M // gr), rp * lr
+
+
+def lane_walk(rows, rp, u):
+    """Per row offset ro < RP of a row block of ``rows`` rows: (passes of u rows, tail rows)."""
+    out = []
+    for ro in range(rp):
+        n = len(range(ro, rows, rp))
+        out.append((n // u, n % u))
+    return out
+
+
 def _gen(seed):
     return torch.Generator().manual_seed(int(seed))
 

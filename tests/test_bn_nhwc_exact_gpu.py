@@ -40,12 +40,7 @@ def _id(v):
 def _geom(M, ch, target, dtype, cc=64):
     """(row blocks, channel chunks, rows per pass) of chunk_grid (cc 64: the statistics
     kernels; 256: the elementwise ones)."""
-    vec = R.VEC[dtype]
-    while cc > vec and not (ch <= cc or ch % cc == 0):
-        cc //= 2
-    ccw = ch if ch <= cc else cc
-    rp, gc = THR // (ccw // vec), ch // ccw
-    return min(max(1, -(-M // (rp * U))), max(1, -(-target // gc)), MAXGR), gc, rp
+    return R.geom(M, ch, target, dtype, cc)[:3]
 
 
 _WS = {}
@@ -59,8 +54,8 @@ def _ws(B):
 
 
 @contextlib.contextmanager
-def _targets(B, stats, handoff=1):
-    B.set_grid_targets(stats, 512, 1024)
+def _targets(B, stats, handoff=1, apply=512, elemt=1024):
+    B.set_grid_targets(stats, apply, elemt)
     B.set_handoff(handoff)
     try:
         yield
@@ -181,6 +176,7 @@ def test_stats_exact_one_level(C, dtype, ch):
     around one pass of the block (RP * U rows) x 1 row block / as many as the rows give."""
     B = C.bn_nhwc
     base = 1025
+    assert R.STATS_ONE_BLOCK[1] in STATS_CH and R.STATS_ONE_BLOCK[0] in DTYPES  # M = 189, target 1 below
     _, _, rp = _geom(base, ch, 512, dtype)
     t = _int_base(base, ch)
     dv = _upload(t, dtype)
@@ -235,7 +231,7 @@ def _fwd_stats(B, x, ch, shift):
     return st
 
 
-def _train_side(save, rm, rv, st, rm0, rv0, momentum, nbt, ch, tag):
+def _train_side(save, rm, rv, st, rm0, rv0, momentum, nbt, ch, tag, sec="b"):
     """Saved mean / invstd and running statistics per channel, from the statistics tensor the
     kernel was given.  Bounds: mean 16 u (|shift| + |s1/n|); variance 16 u (s2/n + (s1/n)^2)
     (its two cancelling terms); invstd relative 16 u plus half the variance bound over
@@ -246,13 +242,13 @@ def _train_side(save, rm, rv, st, rm0, rv0, momentum, nbt, ch, tag):
     mean, var, invstd = R.moments_from_sums(s1, s2, n, sh)
     m1 = s1 / n
     e_mean, e_var = u16 * (sh.abs() + m1.abs()), u16 * (s2 / n + m1 * m1)
-    _within(save[:ch], mean, e_mean, f"{tag} saved mean", "b")
-    _within(save[ch:], invstd, invstd * (u16 + 0.5 * e_var / (var + R.EPS)), f"{tag} saved invstd", "b")
+    _within(save[:ch], mean, e_mean, f"{tag} saved mean", sec)
+    _within(save[ch:], invstd, invstd * (u16 + 0.5 * e_var / (var + R.EPS)), f"{tag} saved invstd", sec)
     mom = momentum if momentum is not None else 1.0 / nbt
     k = n / max(n - 1.0, 1.0)
     erm, erv = R.running_update(rm0, rv0, mean, var, n, momentum, nbt)
-    _within(rm, erm, u16 * (((1 - mom) * rm0).abs() + (mom * mean).abs()) + mom * e_mean, f"{tag} running_mean", "b")
-    _within(rv, erv, u16 * (((1 - mom) * rv0).abs() + mom * k * var) + mom * k * e_var, f"{tag} running_var", "b")
+    _within(rm, erm, u16 * (((1 - mom) * rm0).abs() + (mom * mean).abs()) + mom * e_mean, f"{tag} running_mean", sec)
+    _within(rv, erv, u16 * (((1 - mom) * rv0).abs() + mom * k * var) + mom * k * e_var, f"{tag} running_var", sec)
     return mean, invstd
 
 
@@ -260,62 +256,68 @@ MODES = (("train", 0.1), ("train", None), ("eval", 0.1))
 NBT = 3  # num_batches_tracked handed to the apply kernels (cumulative average: 1/3)
 
 
+def _apply_case(B, kind, M, ch, dtype, sec="b"):
+    t, dv = _elem(kind, M, ch, dtype)
+    st = _fwd_stats(B, dv["x"], ch, dv["rm0"])
+    for (mode, momentum), res, relu in itertools.product(MODES, (False, True), (False, True)):
+        tag = f"apply M={M} {mode} mom={momentum} res={res} relu={relu}"
+        train = mode == "train"
+        rm, rv = dv["rm0"].clone(), dv["rv0"].clone()
+        nbt = torch.full((1,), NBT, dtype=torch.int64, device=DEV)
+        save = torch.full((2 * ch,), NAN, device=DEV)
+        y = torch.full_like(dv["x"], NAN)
+        B.apply(dv["x"], dv["res"] if res else None, y, ch, st if train else torch.zeros_like(st), dv["gamma"],
+                dv["beta"], rm, rv, nbt, -1.0 if momentum is None else momentum, R.EPS, train, relu, save)
+        assert nbt.item() == NBT
+        if train:
+            mean, invstd = _train_side(save, rm, rv, st, t["rm0"], t["rv0"], momentum, NBT, ch, tag, sec)
+        else:
+            mean, invstd = t["rm0"], (t["rv0"] + R.EPS).rsqrt()
+            _same(rm, t["rm0"], f"{tag} running_mean"), _same(rv, t["rv0"], f"{tag} running_var")
+            assert save.isnan().all(), f"{tag}: save written in eval"
+        ref, _, A = R.bn_y(t["x"], mean, invstd, t["gamma"], t["beta"], t["res"] if res else None, relu)
+        _within(y, ref, R.bound(A, ref, dtype), f"{tag} y", sec)
+
+
 @KIND
 @ELEM
 def test_apply_per_element(C, dtype, ch, kind):
-    B = C.bn_nhwc
     for M in R.ELEM_ROWS:
-        t, dv = _elem(kind, M, ch, dtype)
-        st = _fwd_stats(B, dv["x"], ch, dv["rm0"])
-        for (mode, momentum), res, relu in itertools.product(MODES, (False, True), (False, True)):
-            tag = f"apply M={M} {mode} mom={momentum} res={res} relu={relu}"
-            train = mode == "train"
-            rm, rv = dv["rm0"].clone(), dv["rv0"].clone()
-            nbt = torch.full((1,), NBT, dtype=torch.int64, device=DEV)
-            save = torch.full((2 * ch,), NAN, device=DEV)
-            y = torch.full_like(dv["x"], NAN)
-            B.apply(dv["x"], dv["res"] if res else None, y, ch, st if train else torch.zeros_like(st), dv["gamma"],
-                    dv["beta"], rm, rv, nbt, -1.0 if momentum is None else momentum, R.EPS, train, relu, save)
-            assert nbt.item() == NBT
-            if train:
-                mean, invstd = _train_side(save, rm, rv, st, t["rm0"], t["rv0"], momentum, NBT, ch, tag)
-            else:
-                mean, invstd = t["rm0"], (t["rv0"] + R.EPS).rsqrt()
-                _same(rm, t["rm0"], f"{tag} running_mean"), _same(rv, t["rv0"], f"{tag} running_var")
-                assert save.isnan().all(), f"{tag}: save written in eval"
-            ref, _, A = R.bn_y(t["x"], mean, invstd, t["gamma"], t["beta"], t["res"] if res else None, relu)
-            _within(y, ref, R.bound(A, ref, dtype), f"{tag} y", "b")
+        _apply_case(C.bn_nhwc, kind, M, ch, dtype)
+
+
+def _apply_resbn_case(B, kind, M, ch, dtype, sec="b"):
+    t, dv = _elem(kind, M, ch, dtype)
+    s, ds = _elem(kind, M, ch, dtype, extra=500)  # the downsample branch
+    st, rst = _fwd_stats(B, dv["x"], ch, dv["rm0"]), _fwd_stats(B, ds["x"], ch, ds["rm0"])
+    for train in (True, False):
+        tag = f"apply_resbn M={M} train={train}"
+        rm, rv, rrm, rrv = dv["rm0"].clone(), dv["rv0"].clone(), ds["rm0"].clone(), ds["rv0"].clone()
+        nbt = torch.full((1,), NBT, dtype=torch.int64, device=DEV)
+        save, rsave = torch.full((2 * ch,), NAN, device=DEV), torch.full((2 * ch,), NAN, device=DEV)
+        y = torch.full_like(dv["x"], NAN)
+        B.apply_resbn(dv["x"], ds["x"], y, ch, st, dv["gamma"], dv["beta"], rm, rv, nbt, 0.1, R.EPS, save,
+                      rst, ds["gamma"], ds["beta"], rrm, rrv, nbt, -1.0, R.EPS, rsave, train)
+        if train:
+            mean, invstd = _train_side(save, rm, rv, st, t["rm0"], t["rv0"], 0.1, NBT, ch, tag, sec)
+            rmean, rinvstd = _train_side(rsave, rrm, rrv, rst, s["rm0"], s["rv0"], None, NBT, ch, tag + " (r)", sec)
+        else:
+            mean, invstd = t["rm0"], (t["rv0"] + R.EPS).rsqrt()
+            rmean, rinvstd = s["rm0"], (s["rv0"] + R.EPS).rsqrt()
+            for got, want in ((rm, t["rm0"]), (rv, t["rv0"]), (rrm, s["rm0"]), (rrv, s["rv0"])):
+                _same(got, want, f"{tag} running statistics")
+            assert save.isnan().all() and rsave.isnan().all()
+        ref, _, A = R.tail_fwd(t["x"], s["x"], mean, invstd, t["gamma"], t["beta"], rmean, rinvstd, s["gamma"],
+                               s["beta"])
+        _within(y, ref, R.bound(A, ref, dtype), f"{tag} y", sec)
 
 
 @KIND
 @ELEM
 def test_apply_resbn_per_element(C, dtype, ch, kind):
     """relu(bn(x) + bn_r(r)) in one pass: y and both BNs' saves / running statistics."""
-    B = C.bn_nhwc
     for M in R.ELEM_ROWS:
-        t, dv = _elem(kind, M, ch, dtype)
-        s, ds = _elem(kind, M, ch, dtype, extra=500)  # the downsample branch
-        st, rst = _fwd_stats(B, dv["x"], ch, dv["rm0"]), _fwd_stats(B, ds["x"], ch, ds["rm0"])
-        for train in (True, False):
-            tag = f"apply_resbn M={M} train={train}"
-            rm, rv, rrm, rrv = dv["rm0"].clone(), dv["rv0"].clone(), ds["rm0"].clone(), ds["rv0"].clone()
-            nbt = torch.full((1,), NBT, dtype=torch.int64, device=DEV)
-            save, rsave = torch.full((2 * ch,), NAN, device=DEV), torch.full((2 * ch,), NAN, device=DEV)
-            y = torch.full_like(dv["x"], NAN)
-            B.apply_resbn(dv["x"], ds["x"], y, ch, st, dv["gamma"], dv["beta"], rm, rv, nbt, 0.1, R.EPS, save,
-                          rst, ds["gamma"], ds["beta"], rrm, rrv, nbt, -1.0, R.EPS, rsave, train)
-            if train:
-                mean, invstd = _train_side(save, rm, rv, st, t["rm0"], t["rv0"], 0.1, NBT, ch, tag)
-                rmean, rinvstd = _train_side(rsave, rrm, rrv, rst, s["rm0"], s["rv0"], None, NBT, ch, tag + " (r)")
-            else:
-                mean, invstd = t["rm0"], (t["rv0"] + R.EPS).rsqrt()
-                rmean, rinvstd = s["rm0"], (s["rv0"] + R.EPS).rsqrt()
-                for got, want in ((rm, t["rm0"]), (rv, t["rv0"]), (rrm, s["rm0"]), (rrv, s["rv0"])):
-                    _same(got, want, f"{tag} running statistics")
-                assert save.isnan().all() and rsave.isnan().all()
-            ref, _, A = R.tail_fwd(t["x"], s["x"], mean, invstd, t["gamma"], t["beta"], rmean, rinvstd, s["gamma"],
-                                   s["beta"])
-            _within(y, ref, R.bound(A, ref, dtype), f"{tag} y", "b")
+        _apply_resbn_case(C.bn_nhwc, kind, M, ch, dtype)
 
 
 def _bwd_sums(B, dv, ch, act):
@@ -332,40 +334,43 @@ def _fstats(M, ch):
     return fs
 
 
+def _bwd_elemt_case(B, kind, M, ch, dtype, sec="b"):
+    t, dv = _elem(kind, M, ch, dtype)
+    mean, invstd = t["save"][:ch], t["save"][ch:]
+    _, pre, Apre = R.bn_y(t["x"], mean, invstd, t["gamma"], t["beta"])
+    fs = _fstats(M, ch)
+    for act in (0, 1, 2):
+        sums = _bwd_sums(B, dv, ch, act)
+        s64 = _cpu(sums)
+        mask = R.relu_mask(act, y=t["y"], pre=pre)
+        dz = t["dy"] if mask is None else t["dy"] * mask
+        ref, A = R.bn_dx(dz, t["x"], mean, invstd, t["gamma"], s64[:ch], s64[ch:], float(M))
+        keep = None
+        if act == 2 and kind == "float":  # the only skip: the recomputed mask next to its threshold
+            skip = R.near_zero(pre, Apre)
+            assert int(skip.sum()) <= R.skip_allowance(skip.numel())
+            keep = ~skip
+        for with_dres in (False, True):
+            tag = f"bwd_elemt M={M} act={act} dres={with_dres}"
+            dx = torch.full_like(dv["x"], NAN)
+            dres = torch.full_like(dv["x"], NAN) if with_dres else None
+            B.bwd_elemt(dv["dy"], dv["y"] if act == 1 else None, dv["x"], ch, act, dv["save"], sums, fs,
+                        dv["gamma"], dv["beta"], dx, dres)
+            _within(dx, ref, R.bound(A, ref, dtype), f"{tag} dx", sec, keep)
+            if with_dres:
+                _within(dres, dz, torch.zeros_like(dz), f"{tag} dres", sec, keep)
+
+
 @KIND
 @ELEM
 def test_bwd_elemt_per_element(C, dtype, ch, kind):
     """dx per element and dres = dz exactly, act 0 / 1 / 2, with and without dres.  The
     reference starts from the save / sums tensors the kernel was given."""
-    B = C.bn_nhwc
     for M in R.ELEM_ROWS:
-        t, dv = _elem(kind, M, ch, dtype)
-        mean, invstd = t["save"][:ch], t["save"][ch:]
-        _, pre, Apre = R.bn_y(t["x"], mean, invstd, t["gamma"], t["beta"])
-        fs = _fstats(M, ch)
-        for act in (0, 1, 2):
-            sums = _bwd_sums(B, dv, ch, act)
-            s64 = _cpu(sums)
-            mask = R.relu_mask(act, y=t["y"], pre=pre)
-            dz = t["dy"] if mask is None else t["dy"] * mask
-            ref, A = R.bn_dx(dz, t["x"], mean, invstd, t["gamma"], s64[:ch], s64[ch:], float(M))
-            keep = None
-            if act == 2 and kind == "float":  # the only skip: the recomputed mask next to its threshold
-                skip = R.near_zero(pre, Apre)
-                assert int(skip.sum()) <= R.skip_allowance(skip.numel())
-                keep = ~skip
-            for with_dres in (False, True):
-                tag = f"bwd_elemt M={M} act={act} dres={with_dres}"
-                dx = torch.full_like(dv["x"], NAN)
-                dres = torch.full_like(dv["x"], NAN) if with_dres else None
-                B.bwd_elemt(dv["dy"], dv["y"] if act == 1 else None, dv["x"], ch, act, dv["save"], sums, fs,
-                            dv["gamma"], dv["beta"], dx, dres)
-                _within(dx, ref, R.bound(A, ref, dtype), f"{tag} dx", "b", keep)
-                if with_dres:
-                    _within(dres, dz, torch.zeros_like(dz), f"{tag} dres", "b", keep)
+        _bwd_elemt_case(C.bn_nhwc, kind, M, ch, dtype)
 
 
-def _rbn_case(B, kind, M, ch, dtype):
+def _rbn_case(B, kind, M, ch, dtype, sec="b"):
     t, dv = _elem(kind, M, ch, dtype)
     s, ds = _elem(kind, M, ch, dtype, extra=500)
     part, tk = _ws(B)
@@ -389,8 +394,8 @@ def _rbn_case(B, kind, M, ch, dtype):
     else:  # the sums of M terms: first-order bound M u sum|term| (any order), far below a wrong row
         b = R.bn_bwd(t["dy"], s["x"], s["save"][:ch], s["save"][ch:], s["gamma"], mask)
         xh = (s["x"] - s["save"][:ch]) * s["save"][ch:]
-        _within(rout[:ch], b["S1"], M * R.U32 * b["dz"].abs().sum(0), f"{tag} rout S1", "b")
-        _within(rout[ch:], b["S2"], (M + 4) * R.U32 * (b["dz"] * xh).abs().sum(0), f"{tag} rout S2", "b")
+        _within(rout[:ch], b["S1"], M * R.U32 * b["dz"].abs().sum(0), f"{tag} rout S1", sec)
+        _within(rout[ch:], b["S2"], (M + 4) * R.U32 * (b["dz"] * xh).abs().sum(0), f"{tag} rout S2", sec)
         assert torch.equal(rdbeta, rout[:ch]) and torch.equal(rdgamma, rout[ch:])
 
 
@@ -409,6 +414,25 @@ def test_bwd_elemt_rbn_two_level(C):
     gr, gc, _ = _geom(M, ch, 1024, BF, cc=256)
     assert gr == 300 > G1 and gc == 1
     _rbn_case(C.bn_nhwc, "int", M, ch, BF)
+
+
+# One row block: under set_grid_targets(1, 1, 1) the M = 189 inputs above are one row block per
+# channel chunk, so a lane walks whole passes of U rows and then tail rows (under the default
+# targets the row blocks are shorter than one pass for every case but C = 2048, which has no
+# tail).  tests/test_bn_nhwc_ref_cpu.py derives the pass / tail counts of these cases.
+ONE_BLOCK = pytest.mark.parametrize("dtype,ch", R.ONE_BLOCK_CASES + R.ONE_BLOCK_EXTRA, ids=_id)
+
+
+@KIND
+@ONE_BLOCK
+@pytest.mark.parametrize("case", [_apply_case, _apply_resbn_case, _bwd_elemt_case, _rbn_case],
+                         ids=["apply", "apply_resbn", "bwd_elemt", "bwd_elemt_rbn"])
+def test_one_row_block_per_element(C, case, dtype, ch, kind):
+    """The four elementwise checks of this section, same inputs, references, bounds and skip cap."""
+    M = R.ELEM_ROWS[0]
+    assert R.geom(M, ch, 1, dtype, cc=256)[0] == 1
+    with _targets(C.bn_nhwc, 1, apply=1, elemt=1):
+        case(C.bn_nhwc, kind, M, ch, dtype, sec="b, one row block")
 
 
 # =============================================================================== c

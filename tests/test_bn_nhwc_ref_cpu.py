@@ -170,6 +170,42 @@ def test_float_rows_have_the_requested_moments():
         _close(mean, delta.double()), _close(var.sqrt(), sigma.double())
 
 
+def test_one_row_block_cases_walk_a_pass_and_a_tail():
+    """The one-row-block cases of the GPU module: one row block per chunk at M = 189 under
+    targets (1, 1, 1); every active lane makes at least one pass of U rows and some lane then
+    walks a tail row -- except the listed tail-only case, whose dtype another case covers."""
+    Mi = R.ELEM_ROWS[0]
+    full = [c for c in R.ONE_BLOCK_CASES + R.ONE_BLOCK_EXTRA if c not in R.ONE_BLOCK_TAIL_ONLY]
+    assert set(R.ONE_BLOCK_TAIL_ONLY) <= set(R.ONE_BLOCK_CASES)
+    assert {dt for dt, _ in full} == set(R.Q)  # every dtype has a pass + tail case
+    for dt, Ci in R.ONE_BLOCK_CASES + R.ONE_BLOCK_EXTRA:
+        assert (dt, Ci) in R.elem_cases()
+        gr, gc, rp, rows, active = R.geom(Mi, Ci, 1, dt, cc=256)
+        assert gr == 1 and rows == Mi and active <= R.THR
+        walk = R.lane_walk(rows, rp, R.U)
+        if (dt, Ci) in R.ONE_BLOCK_TAIL_ONLY:
+            assert all(p == 0 and t >= 1 for p, t in walk), (dt, Ci, walk)
+        else:
+            assert all(p >= 1 for p, _ in walk) and any(t >= 1 for _, t in walk), (dt, Ci, walk)
+        # under the default targets no lane does both (the gap these cases close)
+        gr, _, rp, rows, _ = R.geom(Mi, Ci, 1024, dt, cc=256)
+        assert not any(p >= 1 and t >= 1 for p, t in R.lane_walk(rows, rp, R.U))
+    # hand counts: bf16 C = 72 is 9 lanes per row, RP = 28, 4 idle lanes; C = 320 five chunks of 64
+    assert R.geom(Mi, 72, 1, torch.bfloat16, cc=256)[1:] == (1, 28, Mi, 252)
+    assert R.geom(Mi, 320, 1, torch.bfloat16, cc=256)[1:] == (5, 32, Mi, 256)
+
+
+def test_statistics_cases_walk_a_pass_and_a_tail():
+    """Section a of the GPU module already holds a one-row-block case in which a lane makes a pass
+    (UF = 8 rows forward, U = 4 backward) and then walks a tail row: fp32, C = 64, M = 189 at
+    target 1 (RP = 16)."""
+    dt, Ci, Mi = R.STATS_ONE_BLOCK
+    gr, gc, rp, rows, _ = R.geom(Mi, Ci, 1, dt)
+    assert (gr, gc, rp, rows) == (1, 1, 16, Mi)
+    for u in (R.UF, R.U):
+        assert any(p >= 1 and t >= 1 for p, t in R.lane_walk(rows, rp, u)), u
+
+
 @pytest.mark.parametrize("dtype,Ci", R.elem_cases(), ids=lambda v: str(v).replace("torch.", ""))
 def test_float_cases_stay_inside_the_skip_allowance(dtype, Ci):
     """The GPU module may skip, per case, at most skip_allowance(numel) elements whose float64
