@@ -22,7 +22,14 @@ Additive flags (all optional; defaults reproduce the reference):
   --model {convnet,resnet50}          resnet50 = BASELINE.json config 5 (ResNet-50, torchvision
                                       layout) on a synthetic ImageNet-shaped set
                                       (--image-size, --num-classes; data/imagenet.py)
-  --resume PATH [--start-epoch N]     load {"model"[, "scaler"]} before training
+  --lr / --momentum / --weight-decay  SGD hyper-parameters (defaults: the reference's SGD(params, 1e-4))
+  --lr-schedule {none,cosine,step}    cosine: --warmup-steps of linear warm-up, then cosine annealing over
+                                      the run's remaining steps, stepped per step; step: x --lr-gamma at
+                                      the --lr-milestones epochs, stepped per epoch.  On the native path
+                                      the schedule lives on the device (optim/lr.py DeviceLR), so the
+                                      graph-replayed steps follow it
+  --resume PATH [--start-epoch N]     load {"model"[, "scaler"][, "optimizer", "lr_scheduler"]} before
+                                      training (the last two are written only with a non-default flag above)
   --watchdog-timeout S                abort + exit when no progress for S seconds (default at
                                       world size > 1: 600, torch's ProcessGroupNCCL default; 0 = off)
   --profile                           roctx ranges (rocprofv3 --marker-trace)
@@ -58,6 +65,14 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
                         help="torch: run the same program on PyTorch's own stack (parity / baseline)")
     parser.add_argument("--model", default="convnet", choices=["convnet", "resnet50"],
                         help="resnet50: ResNet-50 on synthetic 3 x S x S images (BASELINE.json config 5)")
+    parser.add_argument("--lr", type=float, default=1e-4, help="SGD learning rate (the schedule's base rate)")
+    parser.add_argument("--momentum", type=float, default=0.0)
+    parser.add_argument("--weight-decay", type=float, default=0.0)
+    parser.add_argument("--lr-schedule", default="none", choices=["none", "cosine", "step"],
+                        help="cosine: linear warm-up into cosine annealing, per step; step: MultiStepLR, per epoch")
+    parser.add_argument("--warmup-steps", type=int, default=0, help="cosine: steps of linear warm-up")
+    parser.add_argument("--lr-milestones", default="", help="step: comma-separated epochs at which the rate drops")
+    parser.add_argument("--lr-gamma", type=float, default=0.1, help="step: the factor of each drop")
     parser.add_argument("--image-size", type=int, default=224, help="resnet50: synthetic image side")
     parser.add_argument("--num-classes", type=int, default=1000, help="resnet50: synthetic label count")
     if distributed:
@@ -108,10 +123,11 @@ def dist_backend(args) -> str:
     return "xgmi" if getattr(args, "share_gpu", False) else "nccl"
 
 
-def load_checkpoint(path: str, model, scaler=None) -> None:
+def load_checkpoint(path: str, model, scaler=None) -> dict:
     """Load a reference-format checkpoint ({"model": sd[, "scaler": sd]}) without unpickling code.
 
     Accepts both key styles (``layer1.0.weight`` and DDP's ``module.layer1.0.weight``).
+    Returns the file's dict: ``run`` restores "optimizer" / "lr_scheduler" from it once they exist.
     """
     import torch
 
@@ -122,6 +138,41 @@ def load_checkpoint(path: str, model, scaler=None) -> None:
     model.load_state_dict(sd)
     if scaler is not None and "scaler" in ck and ck["scaler"]:
         scaler.load_state_dict(ck["scaler"])
+    return ck
+
+
+WARMUP_START_FACTOR = 0.01  # --lr-schedule cosine: the warm-up's first rate, as a fraction of --lr
+
+
+def lr_flags_default(args) -> bool:
+    """Every optimizer / schedule flag at its default: the run, and its checkpoint, are the reference's."""
+    return (getattr(args, "lr", 1e-4) == 1e-4 and getattr(args, "momentum", 0.0) == 0.0
+            and getattr(args, "weight_decay", 0.0) == 0.0 and getattr(args, "lr_schedule", "none") == "none")
+
+
+def scheduler_factory(args, total_steps: int):
+    """(make_scheduler(optimizer) -> torch scheduler, interval) of --lr-schedule, or (None, None).
+
+    cosine: LinearLR warm-up into CosineAnnealingLR over the run's ``total_steps`` (SequentialLR),
+    stepped per step; step: MultiStepLR over epochs, stepped per epoch."""
+    kind = getattr(args, "lr_schedule", "none")
+    if kind == "none":
+        return None, None
+    from torch.optim import lr_scheduler as S
+
+    if kind == "cosine":
+        warm = max(0, min(int(args.warmup_steps), total_steps - 1))
+
+        def make(opt):
+            cos = S.CosineAnnealingLR(opt, T_max=max(1, total_steps - warm))
+            if warm == 0:
+                return cos
+            lin = S.LinearLR(opt, start_factor=WARMUP_START_FACTOR, total_iters=warm)
+            return S.SequentialLR(opt, [lin, cos], milestones=[warm])
+
+        return make, "step"
+    miles = sorted(int(x) for x in str(args.lr_milestones).split(",") if x.strip())
+    return (lambda opt: S.MultiStepLR(opt, milestones=miles, gamma=args.lr_gamma)), "epoch"
 
 
 DEFAULT_WATCHDOG_S = 600.0  # torch/distributed/constants.py:21 default_pg_timeout (ProcessGroupNCCL)
@@ -171,7 +222,7 @@ class _Metrics:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
-    def epoch(self, epoch: int, images: int, steps: int, scaler=None):
+    def epoch(self, epoch: int, images: int, steps: int, scaler=None, lr=None):
         if self.path is None:
             return
         self._sync()
@@ -180,6 +231,8 @@ class _Metrics:
                "images_per_s": round(images / dt, 1) if dt > 0 else None, "world_size": self.world}
         if scaler is not None and scaler.is_enabled():
             rec["loss_scale"] = scaler.get_scale()
+        if lr is not None:
+            rec["lr"] = lr() if callable(lr) else lr  # one host read per epoch
         with open(self.path, "a") as f:
             f.write(json.dumps(rec) + "\n")
         self.t0 = time.perf_counter()
@@ -270,8 +323,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
         scaler = GradScaler(enabled=True) if amp is not None else None
     else:
         scaler = torch.amp.GradScaler(dev.type) if amp is not None else None
-    if args.resume:
-        load_checkpoint(args.resume, model, scaler)
+    resumed = load_checkpoint(args.resume, model, scaler) if args.resume else {}
     if distributed and native:
         from ddp_practice_amd.parallel import DistributedDataParallel, convert_sync_batchnorm
 
@@ -287,7 +339,9 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
         kw = {} if args.bucket_cap_mb is None else {"bucket_cap_mb": args.bucket_cap_mb}
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[dev.index] if gpu else None, **kw)
     criterion = (CrossEntropyLoss() if native else torch.nn.CrossEntropyLoss()).to(dev)
-    optimizer = SGD(model.parameters(), 1e-4) if native else torch.optim.SGD(model.parameters(), 1e-4)
+    okw = dict(lr=getattr(args, "lr", 1e-4), momentum=getattr(args, "momentum", 0.0),
+               weight_decay=getattr(args, "weight_decay", 0.0))
+    optimizer = SGD(model.parameters(), **okw) if native else torch.optim.SGD(model.parameters(), **okw)
     phase("model")
 
     act_dtype = amp if (amp is not None and gpu) else torch.float32
@@ -319,9 +373,36 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     timeout = watchdog_timeout(args, world)
     watchdog = Watchdog(comm, timeout=timeout, tag=f"rank{rank}") if timeout > 0 else None
     faults = FaultInjector(rank, comm=comm)
+    # The schedule, built once as a torch scheduler: --impl torch steps it; the native path
+    # compiles it into a device table (optim.DeviceLR.from_torch), whose step() is captured
+    # into the step graph.  Position on resume: the file's, else the start of --start-epoch.
+    spe = len(train_dloader)
+    make_sched, interval = scheduler_factory(args, (args.start_epoch + args.epochs) * spe)
+    scheduler = None
+    if make_sched is not None:
+        per = spe if interval == "step" else 1
+        pos = int(resumed.get("lr_scheduler", {}).get("pos", args.start_epoch * per))
+        if native:
+            from ddp_practice_amd.optim import DeviceLR
+
+            scheduler = DeviceLR.from_torch(optimizer, make_sched, (args.start_epoch + args.epochs) * per + 1)
+            scheduler.load_state_dict({"pos": pos})
+        else:
+            import warnings
+
+            scheduler = make_sched(optimizer)
+            with warnings.catch_warnings():  # fast-forward: scheduler steps without optimizer steps
+                warnings.simplefilter("ignore")
+                for _ in range(pos):
+                    scheduler.step()
+    if "optimizer" in resumed:  # the momentum buffers; the hyper-parameters are this run's flags
+        osd = dict(resumed["optimizer"])
+        osd["param_groups"] = optimizer.state_dict()["param_groups"]
+        optimizer.load_state_dict(osd)
     # ResNet-50: hundreds of launches per step, one step per captured graph is enough
     loop = TrainLoop(model, criterion, optimizer, train_dloader, scaler, use_graph=native and not args.no_graph,
-                     steps_per_graph=1 if resnet else 16, watchdog=watchdog, faults=faults)
+                     steps_per_graph=1 if resnet else 16, watchdog=watchdog, faults=faults, scheduler=scheduler,
+                     scheduler_interval=interval or "step")
     metrics = _Metrics(args.metrics_file, rank, world, dev)
     metrics.start()
     try:
@@ -332,7 +413,9 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
                 train_dloader.sampler.set_epoch(epoch)
             loop.run_epoch()
             check_health(comm, f"after epoch {epoch - args.start_epoch + 1}")
-            metrics.epoch(epoch, len(train_dataset), len(train_dloader), scaler)
+            metrics.epoch(epoch, len(train_dataset), len(train_dloader), scaler,
+                          lr=(lambda: scheduler.get_last_lr()[0]) if scheduler is not None
+                          else optimizer.param_groups[0]["lr"])
             phase(f"epoch {epoch}")
         if loop.graph_error is not None and rank == 0:
             print(f"[ddp_practice_amd] hipGraph capture failed, ran eagerly: {loop.graph_error!r}", file=sys.stderr)
@@ -350,6 +433,11 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
                 state = {"model": model.state_dict()}
                 if scaler is not None and distributed:
                     state["scaler"] = scaler.state_dict()
+                if not lr_flags_default(args):
+                    state["optimizer"] = optimizer.state_dict()
+                    if scheduler is not None:
+                        state["lr_scheduler"] = ({"pos": scheduler.state_dict()["pos"]} if native
+                                                 else {"pos": int(scheduler.last_epoch)})
                 torch.save(state, args.checkpoint)
         if distributed and os.environ.get("DPA_CHECKPOINT_EVERY_RANK") == "1":
             # debugging / tests: every rank's own parameters (DDP keeps them bitwise equal)

@@ -83,7 +83,7 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
              unsigned long long* __restrict__ sync, float lr, float momentum, float dampening, float wd, int nesterov,
              int maximize, float growth, float backoff, int interval, const xgmi::XSite& xg, int* __restrict__ err,
              long long barrier_ticks, const SlabSrc& S, int grid, int bid, const int* __restrict__ chk = nullptr,
-             int nchk = 0) {
+             int nchk = 0, const float* __restrict__ lr_dev = nullptr) {
   static_assert(THR == FUSED_THR, "the slab workgroups' lane layout (SLAB_CC columns x SLAB_G row groups)");
   constexpr int BG = THR * U;  // float4 granules per workgroup
   __shared__ int soff[MAXT + 1];
@@ -115,6 +115,15 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
       sp2[tid] = a2;
     }
   }
+  // lr_dev: the device-resident learning rate (optim/lr.py DeviceLR) in place of `lr`: one
+  // word, the same address in every lane.  Issued here, behind the table loads and in front of
+  // the gradients', as a vector load: it returns in order with those, so nothing waits for it
+  // before the gradients are waited for (a scalar load would be waited for by the first LDS
+  // read below, which shares its counter, and so would sit in front of the gradient loads).
+  // No update launch writes the word (the plain and pre-checked modes have no grid barrier: a
+  // late workgroup would read the next step's rate); lr_advance_kernel moves it on,
+  // stream-ordered after this launch.
+  if (lr_dev != nullptr) lr = __hip_atomic_load(lr_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   DPA_STAMP(9);
   const int total = soff[n];

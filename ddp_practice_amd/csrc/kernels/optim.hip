@@ -8,8 +8,12 @@
 //   amp_update_scale  : == torch._amp_update_scale_ (grad_scaler.py:500-537)
 //   flat_copy_scale   : multi-tensor gather into / scatter out of a flat bucket
 //                       with an optional scale (DDP reducer pack/unpack)
+//   lr_advance        : one step of a device-resident learning-rate schedule; every update
+//                       launch reads the rate through an optional lr_dev word in place of
+//                       its by-value lr, so hipGraph replays follow the schedule (optim/lr.py)
 // reference call sites: /root/reference/ddp_main.py:91-93 (scaler.scale/step/update),
 // origin_main.py:87 (SGD lr=1e-4).
+#include <climits>
 #include <cstdlib>
 #include "common.h"
 #include "comm/xgmi.h"
@@ -58,7 +62,11 @@ unscale_check_kernel(MTList L, const float* __restrict__ scale, float* __restric
 // p0 = param, p1 = grad, p2 = momentum buffer (may be null)
 __global__ void __launch_bounds__(NTHR)
 sgd_kernel(MTList L, float lr, float momentum, float dampening, float wd, int nesterov, int maximize,
-           const float* __restrict__ found_inf, const float* __restrict__ grad_scale) {
+           const float* __restrict__ found_inf, const float* __restrict__ grad_scale,
+           const float* __restrict__ lr_dev) {
+  // lr_dev: the device-resident learning rate (optim/lr.py DeviceLR), read in place of `lr`;
+  // issued before the found_inf wait so the two scalar loads are in flight together
+  if (lr_dev != nullptr) lr = lr_dev[0];
   if (found_inf != nullptr && found_inf[0] != 0.f) return;
   const float gs = grad_scale ? 1.f / grad_scale[0] : 1.f;
   const int64_t total = L.chunk_off[L.n];
@@ -110,6 +118,21 @@ __global__ void update_scale_kernel(float* scale, int* tracker, float* found_inf
   }
 }
 
+// The learning-rate schedule on the device (optim/lr.py DeviceLR): table [n][G] holds one
+// row of per-group rates per step.  One wave: pos[0] += 1 (saturating), and the G words the
+// update kernels read (lr_dev) become row min(pos, n - 1) -- past the end the last row
+// holds.  Launched after the update of its step, so stream order is the only ordering the
+// words need; no update launch writes them.
+__global__ void __launch_bounds__(64)
+lr_advance_kernel(const float* __restrict__ table, int n, int G, int* __restrict__ pos,
+                  float* __restrict__ lr_words) {
+  const int p0 = pos[0];  // every lane reads it before lane 0's store below (one wave, program order)
+  const int p = p0 < INT_MAX ? p0 + 1 : p0;
+  const int row = min(max(p, 0), n - 1);
+  for (int g = threadIdx.x; g < G; g += 64) lr_words[g] = table[(int64_t)row * G + g];
+  if (threadIdx.x == 0) pos[0] = p;
+}
+
 // GradScaler.step + SGD + GradScaler.update in ONE launch over a small grid (the
 // ConvNet: 29,034 floats), csrc/kernels/amp_step.h amp_sgd_body.  One optional slab
 // source (ss.nblk > 0): the ConvNet's conv1 weight-gradient slab (optim/sgd.py defer_slab).
@@ -119,12 +142,13 @@ amp_sgd_fused_kernel(MTList L, float* __restrict__ scale, int* __restrict__ trac
                      unsigned long long* __restrict__ sync, float lr, float momentum, float dampening, float wd,
                      int nesterov, int maximize, float growth, float backoff, int interval,
                      xgmi::XSite xg, int* __restrict__ err, long long barrier_ticks, SlabSrc ss, int grid,
-                     const int* __restrict__ chk, int nchk) {
+                     const int* __restrict__ chk, int nchk, const float* __restrict__ lr_dev) {
   // grid == the launch's workgroup count, passed in: gridDim is a load from the hidden kernel
   // arguments on gfx950, and its wait at the top of the kernel came before the table loads
   DPA_STAMP(0);
   amp_sgd_body<U, XG, THR>(L, scale, tracker, found_inf, sync, lr, momentum, dampening, wd, nesterov, maximize,
-                           growth, backoff, interval, xg, err, barrier_ticks, ss, grid, (int)blockIdx.x, chk, nchk);
+                           growth, backoff, interval, xg, err, barrier_ticks, ss, grid, (int)blockIdx.x, chk, nchk,
+                           lr_dev);
 }
 
 // ---------------------------------------------------------------------------
@@ -172,7 +196,7 @@ __global__ void __launch_bounds__(LARGE_THR)
 amp_sgd_large_kernel(const int64_t* __restrict__ table, float* __restrict__ scale, int* __restrict__ tracker,
                      float* __restrict__ found_inf, unsigned long long* __restrict__ sync, float lr, float momentum,
                      float dampening, float wd, int nesterov, int maximize, float growth, float backoff, int interval,
-                     int* __restrict__ err, long long barrier_ticks) {
+                     int* __restrict__ err, long long barrier_ticks, const float* __restrict__ lr_dev) {
   __shared__ long long soff[LARGE_MAXT + 1];
   __shared__ long long snum[LARGE_MAXT];
   __shared__ float* sp0[LARGE_MAXT];
@@ -181,6 +205,9 @@ amp_sgd_large_kernel(const int64_t* __restrict__ table, float* __restrict__ scal
   __shared__ unsigned char sfirst[LARGE_MAXT];
   __shared__ int s_bad;
   const int tid = threadIdx.x;
+  // the device-resident learning rate (never written by this launch): one uniform load,
+  // issued with the table header's
+  if (lr_dev != nullptr) lr = lr_dev[0];
   const int n = (int)table[0];
   const long long total = table[1];
   const int64_t* off = table + 2;
@@ -372,6 +399,15 @@ void unscale_check(std::vector<at::Tensor> grads, at::Tensor scale, at::Tensor f
   });
 }
 
+// the optional device-resident learning rate of an update launch: one f32 word on `like`'s device
+static const float* lr_word(const c10::optional<at::Tensor>& lr_dev, const at::Tensor& like) {
+  if (!lr_dev.has_value()) return nullptr;
+  check_f32(*lr_dev);
+  TORCH_CHECK(lr_dev->numel() == 1 && lr_dev->device() == like.device(),
+              "lr_dev: one f32 word on the parameters' device");
+  return lr_dev->data_ptr<float>();
+}
+
 // first: per tensor, 1 = its momentum buffer is new (b = d, torch's first step); empty = none
 static unsigned long long first_bits(const std::vector<int64_t>& first, size_t s, size_t e) {
   unsigned long long m = 0;
@@ -382,12 +418,14 @@ static unsigned long long first_bits(const std::vector<int64_t>& first, size_t s
 
 void sgd_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, std::vector<at::Tensor> bufs,
               double lr, double momentum, double dampening, double wd, bool nesterov, bool maximize,
-              std::vector<int64_t> first, c10::optional<at::Tensor> found_inf, c10::optional<at::Tensor> grad_scale) {
+              std::vector<int64_t> first, c10::optional<at::Tensor> found_inf, c10::optional<at::Tensor> grad_scale,
+              c10::optional<at::Tensor> lr_dev) {
   TORCH_CHECK(params.size() == grads.size());
   TORCH_CHECK(bufs.empty() || bufs.size() == params.size());
   TORCH_CHECK(first.empty() || first.size() == params.size(), "sgd_step: one first flag per tensor");
   const float* fi = found_inf.has_value() ? found_inf->data_ptr<float>() : nullptr;
   const float* gsp = grad_scale.has_value() ? grad_scale->data_ptr<float>() : nullptr;
+  const float* lrp = params.empty() ? nullptr : lr_word(lr_dev, params[0]);
   for_batches(params.size(), [&](size_t s, size_t e) {
     MTList L{};
     L.n = (int)(e - s);
@@ -404,7 +442,7 @@ void sgd_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, std
       L.chunk_off[k + 1] = L.chunk_off[k] + (L.numel[k] + CHUNK - 1) / CHUNK;
     }
     hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(L.chunk_off[L.n])), dim3(NTHR), 0, cur_stream(), L, (float)lr,
-                       (float)momentum, (float)dampening, (float)wd, (int)nesterov, (int)maximize, fi, gsp);
+                       (float)momentum, (float)dampening, (float)wd, (int)nesterov, (int)maximize, fi, gsp, lrp);
     DPA_CHECK_LAUNCH();
   });
 }
@@ -432,7 +470,8 @@ void amp_sgd_fused(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
                    std::vector<int64_t> first, c10::optional<at::Tensor> scale, c10::optional<at::Tensor> tracker,
                    c10::optional<at::Tensor> found_inf, double growth, double backoff, int64_t interval,
                    at::Tensor sync, std::shared_ptr<xgmi::XgmiComm> xc, c10::optional<at::Tensor> slab,
-                   c10::optional<at::Tensor> slab_out, c10::optional<at::Tensor> prechk) {
+                   c10::optional<at::Tensor> slab_out, c10::optional<at::Tensor> prechk,
+                   c10::optional<at::Tensor> lr_dev) {
   TORCH_CHECK(params.size() == grads.size() && params.size() <= (size_t)MAXT, "fused AMP-SGD: <= ", MAXT,
               " tensors");
   TORCH_CHECK(bufs.empty() || bufs.size() == params.size());
@@ -462,6 +501,7 @@ void amp_sgd_fused(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
   }
   TORCH_CHECK(amp_sgd_resident(), "fused AMP-SGD: grid not co-resident on this device (use the unfused step)");
   MTList L = fused_list(params, grads, bufs, first, momentum);
+  const float* lrp = params.empty() ? nullptr : lr_word(lr_dev, params[0]);
   TORCH_CHECK(slab.has_value() == slab_out.has_value(), "fused AMP-SGD: slab and slab_out go together");
   const SlabSrc ss = slab.has_value() ? slab_src(L, *slab, *slab_out) : SlabSrc{};
   auto launch = [&](auto kern, int bg, xgmi::XSite xg) {
@@ -472,7 +512,7 @@ void amp_sgd_fused(std::vector<at::Tensor> params, std::vector<at::Tensor> grads
                        reinterpret_cast<unsigned long long*>(sync.data_ptr<int64_t>()), (float)lr, (float)momentum,
                        (float)dampening, (float)wd, (int)nesterov, (int)maximize, (float)growth, (float)backoff,
                        (int)interval, xg, reinterpret_cast<int*>(sync.data_ptr<int64_t>() + 3),
-                       (long long)(kBarrierSeconds * 1e8), ss, grid, chk, nchk);
+                       (long long)(kBarrierSeconds * 1e8), ss, grid, chk, nchk, lrp);
   };
   if (xc) {
     const xgmi::XSite xg = xc->grad_site();
@@ -555,7 +595,7 @@ at::Tensor amp_sgd_table(std::vector<at::Tensor> params, std::vector<at::Tensor>
 
 void amp_sgd_large(at::Tensor table, double lr, double momentum, double dampening, double wd, bool nesterov,
                    bool maximize, at::Tensor scale, at::Tensor tracker, at::Tensor found_inf, double growth,
-                   double backoff, int64_t interval, at::Tensor sync) {
+                   double backoff, int64_t interval, at::Tensor sync, c10::optional<at::Tensor> lr_dev) {
   check_f32(scale); check_f32(found_inf);
   TORCH_CHECK(tracker.scalar_type() == at::kInt);
   TORCH_CHECK(table.is_cuda() && table.scalar_type() == at::kLong, "large fused AMP-SGD: table from amp_sgd_table");
@@ -568,7 +608,22 @@ void amp_sgd_large(at::Tensor table, double lr, double momentum, double dampenin
                      reinterpret_cast<unsigned long long*>(sync.data_ptr<int64_t>()), (float)lr, (float)momentum,
                      (float)dampening, (float)wd, (int)nesterov, (int)maximize, (float)growth, (float)backoff,
                      (int)interval, reinterpret_cast<int*>(sync.data_ptr<int64_t>() + 3),
-                     (long long)(kBarrierSeconds * 1e8));
+                     (long long)(kBarrierSeconds * 1e8), lr_word(lr_dev, scale));
+  DPA_CHECK_LAUNCH();
+}
+
+// One step of the device-resident schedule: pos += 1, lr_words = table row min(pos, n - 1).
+void lr_advance(at::Tensor table, at::Tensor pos, at::Tensor lr_words) {
+  check_f32(table); check_f32(lr_words);
+  DPA_CHECK_INPUT(pos);
+  TORCH_CHECK(pos.scalar_type() == at::kInt && pos.numel() == 1, "lr_advance: pos must be int32 [1]");
+  TORCH_CHECK(table.device() == pos.device() && table.device() == lr_words.device(),
+              "lr_advance: table, pos and lr_words on one device");
+  const int64_t G = lr_words.numel();
+  TORCH_CHECK(G >= 1 && table.numel() >= G && table.numel() % G == 0 && table.numel() / G <= INT_MAX,
+              "lr_advance: table must hold n rows of lr_words.numel() rates");
+  hipLaunchKernelGGL(lr_advance_kernel, dim3(1), dim3(64), 0, cur_stream(), table.data_ptr<float>(),
+                     (int)(table.numel() / G), (int)G, pos.data_ptr<int>(), lr_words.data_ptr<float>());
   DPA_CHECK_LAUNCH();
 }
 
@@ -615,7 +670,8 @@ void register_optim(pybind11::module& m) {
   s.def("sgd_step", &opt::sgd_step, pybind11::arg("params"), pybind11::arg("grads"), pybind11::arg("bufs"),
         pybind11::arg("lr"), pybind11::arg("momentum"), pybind11::arg("dampening"), pybind11::arg("weight_decay"),
         pybind11::arg("nesterov"), pybind11::arg("maximize"), pybind11::arg("first") = std::vector<int64_t>{},
-        pybind11::arg("found_inf") = pybind11::none(), pybind11::arg("grad_scale") = pybind11::none());
+        pybind11::arg("found_inf") = pybind11::none(), pybind11::arg("grad_scale") = pybind11::none(),
+        pybind11::arg("lr_dev") = pybind11::none());
   s.def("update_scale", &opt::update_scale);
   s.def("amp_sgd_fused", &opt::amp_sgd_fused, pybind11::arg("params"), pybind11::arg("grads"), pybind11::arg("bufs"),
         pybind11::arg("lr"), pybind11::arg("momentum"), pybind11::arg("dampening"), pybind11::arg("wd"),
@@ -623,12 +679,17 @@ void register_optim(pybind11::module& m) {
         pybind11::arg("tracker"), pybind11::arg("found_inf"), pybind11::arg("growth"), pybind11::arg("backoff"),
         pybind11::arg("interval"), pybind11::arg("sync"), pybind11::arg("xc"),
         pybind11::arg("slab") = pybind11::none(), pybind11::arg("slab_out") = pybind11::none(),
-        pybind11::arg("prechk") = pybind11::none());
+        pybind11::arg("prechk") = pybind11::none(), pybind11::arg("lr_dev") = pybind11::none());
   s.def("amp_sgd_xg_max", &opt::amp_sgd_xg_max);
   s.def("amp_sgd_resident", &opt::amp_sgd_resident);
   s.def("amp_sgd_table", &opt::amp_sgd_table, pybind11::arg("params"), pybind11::arg("grads"), pybind11::arg("bufs"),
         pybind11::arg("first") = std::vector<int64_t>{});
-  s.def("amp_sgd_large", &opt::amp_sgd_large);
+  s.def("amp_sgd_large", &opt::amp_sgd_large, pybind11::arg("table"), pybind11::arg("lr"), pybind11::arg("momentum"),
+        pybind11::arg("dampening"), pybind11::arg("wd"), pybind11::arg("nesterov"), pybind11::arg("maximize"),
+        pybind11::arg("scale"), pybind11::arg("tracker"), pybind11::arg("found_inf"), pybind11::arg("growth"),
+        pybind11::arg("backoff"), pybind11::arg("interval"), pybind11::arg("sync"),
+        pybind11::arg("lr_dev") = pybind11::none());
+  s.def("lr_advance", &opt::lr_advance, pybind11::arg("table"), pybind11::arg("pos"), pybind11::arg("lr_words"));
   s.def("amp_sgd_large_resident", &opt::amp_sgd_large_resident);
   s.attr("LARGE_MAXT") = opt::LARGE_MAXT;
   s.attr("FUSED_MAX") = opt::FUSED_MAX;

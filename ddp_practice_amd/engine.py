@@ -26,18 +26,21 @@ from .runtime.graph import CapturedStep
 from .utils.trace import trace_range
 
 
-def _snapshot(model, optimizer, scaler):
+def _snapshot(model, optimizer, scaler, scheduler=None):
     sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
     opt = {id(p): {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()}
            for p, st in optimizer.state.items()}
     sc = None
     if scaler is not None and getattr(scaler, "_scale", None) is not None:
         sc = (scaler._scale.clone(), scaler._growth_tracker.clone(), scaler._found_inf.clone())
-    return sd, opt, sc
+    # a device-resident schedule (optim.DeviceLR): its position and lr words, which the
+    # warm-up steps of a capture advance like everything else
+    lr = scheduler._snapshot() if hasattr(scheduler, "_snapshot") else None
+    return sd, opt, sc, lr
 
 
-def _restore(model, optimizer, scaler, snap):
-    sd, opt, sc = snap
+def _restore(model, optimizer, scaler, snap, scheduler=None):
+    sd, opt, sc, lr = snap
     with torch.no_grad():
         for k, v in model.state_dict().items():
             v.copy_(sd[k])
@@ -58,18 +61,33 @@ def _restore(model, optimizer, scaler, snap):
         scaler._scale.copy_(sc[0])
         scaler._growth_tracker.copy_(sc[1])
         scaler._found_inf.copy_(sc[2])
+    if lr is not None:
+        scheduler._restore(lr)
 
 
 class TrainLoop:
     """Epoch runner: graph-replayed full batches + eager tail batch."""
 
     def __init__(self, model, criterion, optimizer, loader: DeviceLoader, scaler=None, use_graph: bool = True,
-                 steps_per_graph: int = 16, watchdog=None, faults=None):
+                 steps_per_graph: int = 16, watchdog=None, faults=None, scheduler=None,
+                 scheduler_interval: str = "step"):
         self.model = model
         self.criterion = criterion
         self.optimizer = optimizer
         self.loader = loader
         self.scaler = scaler
+        # scheduler: optim.DeviceLR (its step() is one launch, captured with the step) or, on
+        # an eager loop, any torch scheduler.  "step": stepped after every optimizer update,
+        # unconditionally as a torch loop does (a step found_inf skipped still advances);
+        # "epoch": once at the end of run_epoch, eagerly
+        if scheduler_interval not in ("step", "epoch"):
+            raise ValueError(f"scheduler_interval must be 'step' or 'epoch', not {scheduler_interval!r}")
+        self.scheduler = scheduler
+        self.scheduler_interval = scheduler_interval
+        if scheduler is not None and use_graph and loader.device.type == "cuda" and not hasattr(scheduler, "_snapshot"):
+            # a host-side scheduler edits param_groups[i]["lr"], which a replayed graph never reads
+            raise ValueError("TrainLoop: a captured step replays the learning rate it was captured with; use "
+                             "optim.DeviceLR (DeviceLR.from_torch compiles a torch scheduler) or use_graph=False")
         self.device = loader.device
         self.use_graph = use_graph and self.device.type == "cuda"
         self.spg = max(1, steps_per_graph)
@@ -123,6 +141,8 @@ class TrainLoop:
                 before_update()
             with trace_range("optimizer"):
                 self.optimizer.step()
+        if self.scheduler is not None and self.scheduler_interval == "step":
+            self.scheduler.step()
         return loss
 
     def _eager_step(self, images=None, labels=None, fill=True):
@@ -147,13 +167,14 @@ class TrainLoop:
             return None
         if k in self._graphs:
             return self._graphs[k]
-        snap = _snapshot(self.model, self.optimizer, self.scaler)
+        snap = _snapshot(self.model, self.optimizer, self.scaler, self.scheduler)
         g = CapturedStep(lambda: self._step(), warmup=2, steps_per_graph=k,
-                         pre_capture=lambda: _restore(self.model, self.optimizer, self.scaler, snap))
+                         pre_capture=lambda: _restore(self.model, self.optimizer, self.scaler, snap,
+                                                      self.scheduler))
         ctr = self.loader._ctr.clone() if self.loader._ctr is not None else None
         ok = g.capture()
         # undo the warm-up step's data consumption and parameter update
-        _restore(self.model, self.optimizer, self.scaler, snap)
+        _restore(self.model, self.optimizer, self.scaler, snap, self.scheduler)
         if ctr is not None:
             self.loader._ctr.copy_(ctr)
         if not ok:
@@ -199,6 +220,8 @@ class TrainLoop:
                 imgs, labels = self.loader.static_batch(b)
                 self.loader._fill_tail(imgs, labels, nfull + i)
                 self._eager_step(imgs, labels, fill=False)
+        if self.scheduler is not None and self.scheduler_interval == "epoch":
+            self.scheduler.step()
 
 
 @torch.no_grad()

@@ -1,2 +1,3 @@
-"""Optimizers (multi-tensor HIP kernels)."""
+"""Optimizers (multi-tensor HIP kernels) and the device-resident learning-rate schedule."""
+from .lr import DeviceLR  # noqa: F401
 from .sgd import SGD  # noqa: F401

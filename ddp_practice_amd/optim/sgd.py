@@ -99,6 +99,12 @@ class SGD(Optimizer):
         if ps is not None:
             _load_ext().convblock.slab_reduce(ps[0], ps[1].numel(), ps[1])
 
+    def _lr_kw(self, gi: int = 0) -> dict:
+        """``lr_dev=`` of group ``gi``'s update launch: its device-resident rate when an
+        ``optim.DeviceLR`` is attached (optim/lr.py), else nothing -- the call is today's."""
+        w = self.__dict__.get("_lr_words")
+        return {} if w is None else {"lr_dev": w[gi]}
+
     def _flush_deferred(self):
         """Average gradients a DDP reducer left to this optimizer (DDP.defer_grad_sync_to)
         and sum a deferred gradient slab (defer_slab)."""
@@ -117,7 +123,7 @@ class SGD(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for group, params, grads, bufs, first in self._collect():
+        for gi, (group, params, grads, bufs, first) in enumerate(self._collect()):
             if not params:
                 continue
             native = params[0].is_cuda and all(
@@ -126,11 +132,12 @@ class SGD(Optimizer):
             if native:
                 _load_ext().optim.sgd_step(params, grads, bufs, group["lr"], group["momentum"], group["dampening"],
                                            group["weight_decay"], group["nesterov"], group["maximize"], first,
-                                           found_inf, None)
+                                           found_inf, None, **self._lr_kw(gi))
             else:
                 if found_inf is not None and bool(found_inf.item()):
                     continue
-                self._torch_step(group, params, grads, bufs, first)
+                w = self.__dict__.get("_lr_words")
+                self._torch_step(group, params, grads, bufs, first, None if w is None else float(w[gi]))
         return loss
 
     # ------------------------------------------------------------------ AMP
@@ -239,7 +246,7 @@ class SGD(Optimizer):
             self._flush_deferred()
             O.amp_sgd_large(self._large_table(params, grads, bufs, first), group["lr"], group["momentum"],
                             group["dampening"], group["weight_decay"], group["nesterov"], group["maximize"],
-                            scale, tracker, found_inf, growth, backoff, interval, sync)
+                            scale, tracker, found_inf, growth, backoff, interval, sync, **self._lr_kw())
             return
         # gradients a DDP reducer deferred to this step are averaged inside the kernel
         d = getattr(self, "_deferred_ddp", None)
@@ -258,7 +265,8 @@ class SGD(Optimizer):
         O.amp_sgd_fused(params, grads, bufs, group["lr"], group["momentum"], group["dampening"],
                         group["weight_decay"], group["nesterov"], group["maximize"], first,
                         scale, tracker, found_inf, growth, backoff, interval, sync, xc,
-                        ps[0] if ps is not None else None, ps[1] if ps is not None else None, prechk)
+                        ps[0] if ps is not None else None, ps[1] if ps is not None else None, prechk,
+                        **self._lr_kw())
         if xc is not None:
             d[0].consume_deferred()
 
@@ -279,13 +287,15 @@ class SGD(Optimizer):
         _load_ext().optim.amp_sgd_fused(params, grads, bufs, group["lr"], group["momentum"], group["dampening"],
                                         group["weight_decay"], group["nesterov"], group["maximize"], first,
                                         None, None, None, 1.0, 1.0, 1, sync, xc,
-                                        ps[0] if ps is not None else None, ps[1] if ps is not None else None)
+                                        ps[0] if ps is not None else None, ps[1] if ps is not None else None,
+                                        **self._lr_kw())
         if xc is not None:
             d[0].consume_deferred()
 
     @staticmethod
-    def _torch_step(group, params, grads, bufs, first):
-        lr, mom, damp, wd = group["lr"], group["momentum"], group["dampening"], group["weight_decay"]
+    def _torch_step(group, params, grads, bufs, first, lr=None):
+        lr = group["lr"] if lr is None else lr  # lr: the group's DeviceLR word, read on the host
+        mom, damp, wd = group["momentum"], group["dampening"], group["weight_decay"]
         for i, (p, g) in enumerate(zip(params, grads)):
             d = -g if group["maximize"] else g
             if wd != 0:
