@@ -46,43 +46,77 @@ struct BwdEpi {
 // exactly the LDS tile layout conv5x5_kernel uses (rows padded to KPW, K
 // padding zeroed): the forward tile [32][424] (k = tap*16 + ci) and the
 // data-grad tile [16][808] (k = (24-tap)*32 + co, the flipped transpose).
-// The layer-1 forward kernel writes them as a side job (its workgroups are
-// idle for most of the chip anyway), so the layer-2 kernels stage their weight
-// tile with straight 16-B copies instead of 12,800 converted, scattered
-// element stores per workgroup (the VALU-heaviest part of their staging).
+// The layer-1 forward launch writes them as a side job: W2P_WGS workgroups of
+// their own appended behind its conv workgroups (conv5x5_kernel WPK 2; the conv
+// workgroups leave most of the chip idle anyway), so the layer-2 kernels stage
+// their weight tile with straight 16-B copies instead of 12,800 converted,
+// scattered element stores per workgroup (the VALU-heaviest part of their
+// staging), and the conv workgroups do not carry the pack's memory round trips
+// ahead of their own.
 // ---------------------------------------------------------------------------
 constexpr int W2F_ROWS = 32, W2F_PITCH = 424;   // ceil_to(25*16, 32) + 8
 constexpr int W2D_ROWS = 16, W2D_PITCH = 808;   // ceil_to(25*32, 32) + 8
 constexpr int W2F_LEN = W2F_ROWS * W2F_PITCH, W2D_LEN = W2D_ROWS * W2D_PITCH;
+// the pack workgroups of a launch and the elements per lane: fixed, whatever the batch
+constexpr int W2P_WGS = 26, W2P_IT = 4;
+static_assert(W2P_WGS * W2P_IT * NTHR >= W2F_LEN + W2D_LEN, "the pack workgroups cover both packs");
 template <typename T>
 struct WPack {
   const float* w2 = nullptr;  // [32][16][5][5] f32 master weights
   T* fwd = nullptr;           // [W2F_LEN]
   T* dgrad = nullptr;         // [W2D_LEN]
 };
+// Pack workgroup wg of W2P_WGS: element (wg * W2P_IT + i) * NTHR + lane of
+// [fwd | dgrad].  Compile-time trip counts and no blockDim / gridDim (hidden-argument loads
+// with a wait of their own); every w2 load is issued (clamped, unconditional: the padding
+// columns and the lanes past the end read a valid element they do not use) before the first
+// conversion or store, so the role is one memory round trip.
 template <typename T>
-__device__ __forceinline__ void pack_w2(const WPack<T>& pk) {
-  const int total = W2F_LEN + W2D_LEN;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+__device__ __forceinline__ void pack_w2(const WPack<T>& pk, const int wg) {
+  constexpr int TOTAL = W2F_LEN + W2D_LEN;
+  const int tid = threadIdx.x;
+  DPA_STAMP(0);
+  float v[W2P_IT];
+  bool pad[W2P_IT];
+#pragma unroll
+  for (int i = 0; i < W2P_IT; ++i) {
+    const int e = min((wg * W2P_IT + i) * NTHR + tid, TOTAL - 1);
+    int src;
     if (e < W2F_LEN) {
-      const int co = e / W2F_PITCH, k = e % W2F_PITCH;
-      const float v = k < 400 ? pk.w2[(co * 16 + (k & 15)) * 25 + (k >> 4)] : 0.f;
-      pk.fwd[e] = Cvt<T>::from_f(v);
+      const int co = e / W2F_PITCH, k = e % W2F_PITCH, kk = min(k, 399);
+      pad[i] = k >= 400;
+      src = (co * 16 + (kk & 15)) * 25 + (kk >> 4);
     } else {
       const int e2 = e - W2F_LEN;
-      const int ci = e2 / W2D_PITCH, k = e2 % W2D_PITCH;
-      const float v = k < 800 ? pk.w2[((k & 31) * 16 + ci) * 25 + (24 - (k >> 5))] : 0.f;
-      pk.dgrad[e2] = Cvt<T>::from_f(v);
+      const int ci = e2 / W2D_PITCH, k = e2 % W2D_PITCH, kk = min(k, 799);
+      pad[i] = k >= 800;
+      src = ((kk & 31) * 16 + ci) * 25 + (24 - (kk >> 5));
     }
+    v[i] = pk.w2[src];  // src < 32 * 16 * 25
   }
+#pragma unroll
+  for (int i = 0; i < W2P_IT; ++i) {
+    const int e = (wg * W2P_IT + i) * NTHR + tid;
+    const T o = Cvt<T>::from_f(pad[i] ? 0.f : v[i]);
+    if (e < W2F_LEN)
+      pk.fwd[e] = o;
+    else if (e < TOTAL)
+      pk.dgrad[e - W2F_LEN] = o;
+  }
+  DPA_STAMP(7);
 }
 
 // Batch gather fused into the first conv (PRO 3): the input image is read from
 // the uint8 dataset resident in HBM through the epoch's sample order at the
 // device step counter, converted (ToTensor: x * scale + shift, data/loader.py)
 // and staged; split 0 of each image also writes it (and its label) to the
-// batch buffers the rest of the step reads.  The launch's last-arriving
-// workgroup advances the step counter (data.hip gather_kernel's protocol).
+// batch buffers the rest of the step reads.  The launch's last-arriving conv
+// workgroup advances the step counter (data.hip gather_kernel's protocol); a
+// workgroup arrives as its last act, after its partial-sum row is stored, so no
+// wave waits for the atomic's return ahead of the compute barrier.
+// Only counter -> order[pos] -> pixels depend on each other: the counter load is
+// the workgroup's first memory instruction, bias / shift / weights are issued
+// behind it, and the LDS zeroing and the weight scatter run under the order load.
 struct GatherIn {
   const uint8_t* imgs = nullptr;   // [N][npix]
   const int64_t* labels = nullptr; // [N]
@@ -91,8 +125,9 @@ struct GatherIn {
   int* ctr = nullptr;              // [0] step, [1] arrivals (self-resetting)
   int64_t* lab_out = nullptr;      // [B]
   float scale = 1.f, shift = 0.f;
-  int nimg = 0;                    // B (the launch has nimg * nsplit workgroups; not gridDim,
-                                   // a hidden-argument load with its own wait on gfx950)
+  int nimg = 0;                    // B (the launch has nimg * nsplit conv workgroups; not gridDim,
+                                   // a hidden-argument load with its own wait on gfx950).  Set by
+                                   // every WPK 2 launch: the workgroups from nimg * nsplit on pack
 };
 
 // ---------------------------------------------------------------------------
@@ -117,7 +152,9 @@ struct GatherIn {
 //          BN partial sums [S1 | S2] of the block below (epi).
 //   WPK 0: stage the weight tile from the f32 master weights w;
 //   WPK 1: w is ignored, the tile is copied from the pre-packed wpk (pack_w2);
-//   WPK 2: as 0, and this launch also writes the layer-2 packs (pk).
+//   WPK 2: (CIN 1, PRO 0 / 3) as 0 with every load of the prologue issued before the first
+//          wait, and this launch also writes the layer-2 packs (pk) in W2P_WGS workgroups
+//          appended behind the gin.nimg * nsplit conv workgroups (conv5x5_kernel).
 // bid: this workgroup's index among the launch's workgroups of this role (blockIdx.x
 // for a launch of its own; conv5x5_kernel / dgrad_wgrad_kernel below).
 // DYN: the two big LDS tiles (image, weights) are carved from the launch's dynamic LDS
@@ -192,6 +229,16 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   const int tid = threadIdx.x;
   const int b = bid / nsplit;
   DPA_STAMP(0);
+  // C1: the fused step's first conv (WPK 2).  Its prologue issues every global load before the
+  // first wait; with the gather (PRO 3) the step counter's load goes first: counter -> order ->
+  // pixels is the workgroup's one dependent chain (GatherIn)
+  constexpr bool C1 = WPK == 2;
+  static_assert(!C1 || (CIN == 1 && MODE != 2 && EPI == 0 && (PRO == 0 || PRO == 3)), "WPK 2: the first conv");
+  static_assert(PRO != 3 || C1, "the gather prologue belongs to the fused step's first conv");
+  int step = 0, step_v = 0;
+  // (a relaxed atomic load: the previous launch's atomic store is visible at this launch's start;
+  //  a volatile load is waited for right where it is issued)
+  if constexpr (PRO == 3) step_v = __hip_atomic_load(gin.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int sp = bid % nsplit;
   const T* xb = x + (size_t)b * CIN * HW;
   const int mt0 = (MT * sp) / nsplit, mt1 = (MT * (sp + 1)) / nsplit;
@@ -254,7 +301,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   };
   if constexpr (WPK == 1) {
     if constexpr (PRO == 0 || PRO == 3) load_wpk();
-  } else {
+  } else if constexpr (!C1) {
     if constexpr (KP > K) {
       for (int e = tid; e < COUT * (KP - K); e += NTHR) wl[(e / (KP - K)) * KPW + K + e % (KP - K)] = zero;
     }
@@ -270,11 +317,12 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
         wl[o * KPW + tap * CIN + i] = Cvt<T>::from_f(v);
     });
   }
-  if constexpr (WPK == 2) pack_w2<T>(pk);
   DPA_STAMP(1);
   // --- stage the zero-padded image in HWC order: zero the halo pixels
   //     (whole 16-B groups when a pixel is, else element by element)
-  if constexpr ((CIN * sizeof(T)) % 16 == 0) {
+  if constexpr (C1) {
+    // (the first conv zeroes its halo under its loads: fill_lds below)
+  } else if constexpr ((CIN * sizeof(T)) % 16 == 0) {
     constexpr int G = CIN * (int)sizeof(T) / 16;  // 16-B groups per pixel
     uint4* img4 = reinterpret_cast<uint4*>(img);
     if constexpr (WIN) {  // the halo pixels of the padded rows this workgroup reads
@@ -351,52 +399,107 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   uint8_t dq_i[DQ];
 #pragma unroll
   for (int d = 0; d < DQ; ++d) dq_e[d] = -1;
-  if constexpr (PRO == 0) {
+  if constexpr (C1) {
+    // the weights as one float4 per lane (clamped: the load stays unconditional), issued
+    // behind the bias / shift loads (and the counter's) with no wait in between
+    constexpr int WN4 = COUT * K / 4;
+    static_assert((COUT * K) % 4 == 0 && WN4 <= NTHR, "one float4 of the weights per lane");
+    const f32x4 w4 = reinterpret_cast<const f32x4*>(w)[min(tid, WN4 - 1)];
+    // the LDS work that needs no global data (K padding of the weight tile, the halo), then the
+    // weight scatter to wl[co][tap]: run while the input's loads are in flight
+    auto fill_lds = [&]() {
+      for (int e = tid; e < COUT * (KP - K); e += NTHR) wl[(e / (KP - K)) * KPW + K + e % (KP - K)] = zero;
+      for (int e = tid; e < HP * WPD; e += NTHR) {
+        const int hp = e / WPD, wp = e % WPD;
+        if (hp < 2 || hp >= H + 2 || wp < 2 || wp >= W + 2) img[e] = zero;
+      }
+      if (tid < WN4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int e = 4 * tid + j;
+          wl[(e / 25) * KPW + e % 25] = Cvt<T>::from_f(w4[j]);
+        }
+      }
+    };
+    if constexpr (PRO == 0) {
+      typedef typename Pair2<T>::type P;
+      static_assert(W % 2 == 0, "pixel pairs stay inside a row");
+      constexpr int NP = HW / 2, XIT = (NP + NTHR - 1) / NTHR;
+      const P* s2 = reinterpret_cast<const P*>(xb);
+      P xv[XIT];
+#pragma unroll
+      for (int i = 0; i < XIT; ++i) xv[i] = s2[min(tid + i * NTHR, NP - 1)];
+      fill_lds();
+      DPA_STAMP(3);
+#pragma unroll
+      for (int i = 0; i < XIT; ++i) {
+        const int e = tid + i * NTHR;
+        if (e < NP) {
+          const int h = (2 * e) / W, ww = (2 * e) % W;
+          T a, bb;
+          __builtin_memcpy(&a, &xv[i], sizeof(T));
+          __builtin_memcpy(&bb, reinterpret_cast<const char*>(&xv[i]) + sizeof(T), sizeof(T));
+          img[imo((h + 2) * WPD + (ww + 2), 0)] = a;
+          img[imo((h + 2) * WPD + (ww + 3), 0)] = bb;
+        }
+      }
+    } else {
+      // step counter -> sample -> 4 uint8 pixels per lane load
+      static_assert(HW % 4 == 0 && W % 4 == 0, "4-pixel groups stay inside a row");
+      constexpr int G4 = HW / 4, GIT = (G4 + NTHR - 1) / NTHR;
+      step = __builtin_amdgcn_readfirstlane(step_v);  // waits for the counter alone: it was issued first
+      DPA_STAMP(8);
+      long long pos = (long long)step * gin.nimg + b;
+      pos = pos < gin.order_len ? pos : gin.order_len - 1;  // never taken with a correct host-side batch count
+      const int64_t src_v = gin.order[pos];
+      fill_lds();
+      DPA_STAMP(3);
+      // wave-uniform: the sample's base addresses stay scalar
+      const uint32_t src_lo = __builtin_amdgcn_readfirstlane((uint32_t)src_v);
+      const uint32_t src_hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)src_v >> 32));
+      const int64_t src = (int64_t)(((uint64_t)src_hi << 32) | src_lo);
+      DPA_STAMP(9);
+      const uint32_t* s4 = reinterpret_cast<const uint32_t*>(gin.imgs + src * HW);
+      uint32_t v4[GIT];
+#pragma unroll
+      for (int i = 0; i < GIT; ++i) v4[i] = s4[min(tid + i * NTHR, G4 - 1)];  // clamped: unconditional
+      const int64_t lab_v = gin.labels[src];  // every lane (one address): no branch around the load
+      T px[GIT][4];
+#pragma unroll
+      for (int i = 0; i < GIT; ++i) {
+        const int g = tid + i * NTHR;
+        const int h = (4 * g) / W, ww = (4 * g) % W;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          px[i][k] = Cvt<T>::from_f((float)((v4[i] >> (8 * k)) & 0xffu) * gin.scale + gin.shift);
+          if (g < G4) img[imo((h + 2) * WPD + (ww + k + 2), 0)] = px[i][k];
+        }
+      }
+      // taken by every wave, here, right behind the pixels: left pending on the waves that do not
+      // store it, the load would be waited for with vmcnt(0) wherever its registers are reused --
+      // after the compute barrier and after the MFMA loop, behind this wave's own stores
+      const uint32_t lab_lo = __builtin_amdgcn_readfirstlane((uint32_t)lab_v);
+      const uint32_t lab_hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)lab_v >> 32));
+      const int64_t lab = (int64_t)(((uint64_t)lab_hi << 32) | lab_lo);
+      DPA_STAMP(10);
+      if (sp == 0) {  // the batch buffers (conv1's weight gradient, the loss and the user read them)
+        T* xo = const_cast<T*>(xb);
+#pragma unroll
+        for (int i = 0; i < GIT; ++i) {
+          const int g = tid + i * NTHR;
+          if (g < G4) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) xo[4 * g + k] = px[i][k];
+          }
+        }
+        if (tid == 0) gin.lab_out[b] = lab;
+      }
+    }
+  } else if constexpr (PRO == 0) {
     stage_chw<T, CIN, H, W>(xb, [&](int ci, int h, int ww, T a, T bb) {
       img[imo((h + 2) * WPD + (ww + 2), ci)] = a;
       img[imo((h + 2) * WPD + (ww + 3), ci)] = bb;
     });
-  } else if constexpr (PRO == 3) {
-    // step counter -> sample -> 4 uint8 pixels per lane load
-    static_assert(HW % 4 == 0 && W % 4 == 0, "4-pixel groups stay inside a row");
-    constexpr int G4 = HW / 4, GIT = (G4 + NTHR - 1) / NTHR;
-    const int step = __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile int*>(gin.ctr));
-    long long pos = (long long)step * gin.nimg + b;
-    pos = pos < gin.order_len ? pos : gin.order_len - 1;  // never taken with a correct host-side batch count
-    const int64_t src = gin.order[pos];
-    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(gin.imgs + src * HW);
-    uint32_t v4[GIT];
-#pragma unroll
-    for (int i = 0; i < GIT; ++i)
-      if (tid + i * NTHR < G4) v4[i] = s4[tid + i * NTHR];
-    if (sp == 0 && tid == 0) gin.lab_out[b] = gin.labels[src];
-    T* xo = const_cast<T*>(xb);
-#pragma unroll
-    for (int i = 0; i < GIT; ++i) {
-      const int g = tid + i * NTHR;
-      if (g < G4) {
-        const int h = (4 * g) / W, ww = (4 * g) % W;
-        T px[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          px[k] = Cvt<T>::from_f((float)((v4[i] >> (8 * k)) & 0xffu) * gin.scale + gin.shift);
-          img[imo((h + 2) * WPD + (ww + k + 2), 0)] = px[k];
-        }
-        if (sp == 0) {  // the batch buffer (conv1's weight gradient and the user read it)
-#pragma unroll
-          for (int k = 0; k < 4; ++k) xo[4 * g + k] = px[k];
-        }
-      }
-    }
-    // advance the step counter once every workgroup has read it (relaxed: the next
-    // launch reads it after this one completes)
-    if (tid == 0) {
-      const int arrived = __hip_atomic_fetch_add(&gin.ctr[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (arrived == gin.nimg * nsplit - 1) {
-        __hip_atomic_store(&gin.ctr[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&gin.ctr[0], step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
   } else if constexpr (PRO == 1) {
     __shared__ float sc_s[CIN], beta_s[CIN], mean_s[CIN], istd_s[CIN];
     __shared__ float part[NTHR];
@@ -655,6 +758,19 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
       if (bid == 0 && tid < COUT) fstats[2 * COUT + 1 + tid] = shift[tid];
     }
   }
+  if constexpr (PRO == 3) {
+    // arrive, as this workgroup's last act (nothing here needs the atomic's return but the
+    // completing workgroup); the last of the launch's nimg * nsplit conv workgroups advances
+    // the step counter: every one of them has read it by then (relaxed: the next launch reads
+    // it after this one completes)
+    if (tid == 0) {
+      const int arrived = __hip_atomic_fetch_add(&gin.ctr[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (arrived == gin.nimg * nsplit - 1) {
+        __hip_atomic_store(&gin.ctr[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&gin.ctr[0], step + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
   DPA_STAMP(7);
 }
 
@@ -665,6 +781,13 @@ conv5x5_kernel(const T* __restrict__ x, const float* __restrict__ w, const float
                const float* __restrict__ shift, int nsplit, PoolIn<T> pin = PoolIn<T>{},
                BwdIn<T> bin = BwdIn<T>{}, BwdEpi<T> epi = BwdEpi<T>{}, const T* __restrict__ wpk = nullptr,
                WPack<T> pk = WPack<T>{}, GatherIn gin = GatherIn{}) {
+  if constexpr (WPK == 2) {  // the workgroups behind the conv role's pack the layer-2 weights
+    const int nconv = gin.nimg * nsplit;
+    if ((int)blockIdx.x >= nconv) {
+      pack_w2<T>(pk, (int)blockIdx.x - nconv);
+      return;
+    }
+  }
   conv5x5_body<T, CIN, COUT, H, W, MODE, PRO, EPI, WPK, false, WR>(x, w, bias, y, fslab, fstats, shift, nsplit, pin,
                                                                    bin, epi, wpk, pk, (int)blockIdx.x, gin);
 }

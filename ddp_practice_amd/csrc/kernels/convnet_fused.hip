@@ -393,7 +393,8 @@ static void check_conv1_pack(const at::Tensor& x, const at::Tensor& w1, const at
               wpk_f.scalar_type() == x.scalar_type() && wpk_d.scalar_type() == x.scalar_type());
 }
 
-// Layer-1 conv (+BN1 sums when training) that also packs the layer-2 weights (cb::pack_w2).
+// Layer-1 conv (+BN1 sums when training) whose launch also packs the layer-2 weights: B * SPLIT conv
+// workgroups, then cb::W2P_WGS pack workgroups (cb::pack_w2), which write no fslab1 row.
 void conv1_fwd_pack(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor y1, c10::optional<at::Tensor> fslab1,
                     c10::optional<at::Tensor> fstats1, c10::optional<at::Tensor> shift1, at::Tensor w2,
                     at::Tensor wpk_f, at::Tensor wpk_d) {
@@ -410,15 +411,18 @@ void conv1_fwd_pack(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor y1, c
   with_t(dt_of(x), [&](auto tag) {
     typedef decltype(tag) T;
     cb::WPack<T> pk{w2.data_ptr<float>(), dptr<T>(wpk_f), dptr<T>(wpk_d)};
+    cb::GatherIn gin;  // no gather: just the conv workgroup count (the pack role starts behind it)
+    gin.nimg = B;
     if (st)
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 0, 0, 0, 2>), dim3(B * S::SPLIT), dim3(cb::NTHR), 0,
-                         cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(), dptr<T>(y1),
-                         fslab1->data_ptr<float>(), fstats1->data_ptr<float>(), shift1->data_ptr<float>(), S::SPLIT,
-                         PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{}, nullptr, pk);
+      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 0, 0, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS),
+                         dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(),
+                         dptr<T>(y1), fslab1->data_ptr<float>(), fstats1->data_ptr<float>(),
+                         shift1->data_ptr<float>(), S::SPLIT, PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{}, nullptr, pk, gin);
     else
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 1, 0, 0, 2>), dim3(B * S::SPLIT), dim3(cb::NTHR), 0,
-                         cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(), dptr<T>(y1), nullptr,
-                         nullptr, nullptr, S::SPLIT, PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{}, nullptr, pk);
+      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 1, 0, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS),
+                         dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(),
+                         dptr<T>(y1), nullptr, nullptr, nullptr, S::SPLIT, PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{},
+                         nullptr, pk, gin);
   });
   DPA_CHECK_LAUNCH();
 }
@@ -457,10 +461,10 @@ void conv1_fwd_pack_gather(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tenso
   with_t(dt_of(x), [&](auto tag) {
     typedef decltype(tag) T;
     cb::WPack<T> pk{w2.data_ptr<float>(), dptr<T>(wpk_f), dptr<T>(wpk_d)};
-    hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 0, 3, 0, 2>), dim3(B * S::SPLIT), dim3(cb::NTHR), 0,
-                       cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(), dptr<T>(y1),
-                       fslab1.data_ptr<float>(), fstats1.data_ptr<float>(), shift1.data_ptr<float>(), S::SPLIT,
-                       PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{}, nullptr, pk, gin);
+    hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 0, 3, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS),
+                       dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(),
+                       dptr<T>(y1), fslab1.data_ptr<float>(), fstats1.data_ptr<float>(), shift1.data_ptr<float>(),
+                       S::SPLIT, PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{}, nullptr, pk, gin);
   });
   DPA_CHECK_LAUNCH();
 }

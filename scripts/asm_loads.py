@@ -44,7 +44,7 @@ def main() -> int:
             k = 0
             for i, line in enumerate(f.splitlines()):
                 t = line.strip()
-                if re.match(r"(global_load|buffer_load|s_waitcnt vmcnt|s_barrier|global_atomic|global_store|s_sleep)", t):
+                if re.match(r"(global_load|flat_load|buffer_load|s_waitcnt vmcnt|s_barrier|global_atomic|global_store|s_sleep)", t):
                     print(f"{i:6d}  {t[:90]}")
                     k += 1
                     if k >= n:

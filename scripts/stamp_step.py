@@ -3,10 +3,16 @@
     DPA_EXT_SO=ddp_practice_amd/_C_timing.so python scripts/stamp_step.py [--forced]
 --forced: the W>1 step shape on one GPU (DDP + SyncBN with every collective forced at W=1,
 the xGMI engine's in-kernel exchanges), as bench.py --force-collectives.
-For the head step (convnet_head.head_step) and the merged layer-2 backward
-(convnet.conv2_bwd, roles split by block range): blocks, span (first start ->
-last stamp), start skew, and the mean time of each stamped phase relative to
-the block's own start (us)."""
+For the head step (convnet_head.head_step), the first conv with the batch gather
+(convnet.conv1_fwd_pack_gather: its conv workgroups and the pack workgroups behind them)
+and the merged layer-2 backward (convnet.conv2_bwd), roles split by block range: blocks,
+span (first start -> last stamp), start skew, and the mean / max time of each stamped phase
+relative to the block's own start (us).
+conv1/conv phases: s1, s2 prologue loads issued; s8 step counter returned; s3 LDS zeroing and
+weight scatter done; s9 order[pos] returned; s10 pixels returned and staged; s4 / s5 before /
+after the compute barrier; s6 MFMA loop done; s7 end (row stored, arrival issued).  On a build
+whose conv workgroups pack the weights themselves: s1 weights staged and packed, s2 halo
+zeroed, s4 gather done and arrived."""
 import os
 import sys
 
@@ -79,6 +85,8 @@ NFW = int(C.convnet.fwd2_split(False)) * B      # conv2 forward workgroups
 wrap(C.convnet_head, "head_step", lambda a: [("head_step", slice(0, 32))])
 wrap(C.convnet, "conv2_bwd", lambda a: [("conv2_bwd/dgrad", slice(0, NDG)),
                                          ("conv2_bwd/wgrad", slice(NDG, NDG + 4 * B))])
+for _n in ("conv1_fwd_pack_gather", "conv1_fwd_pack"):
+    wrap(C.convnet, _n, lambda a: [("conv1/conv", slice(0, 4 * B)), ("conv1/pack", slice(4 * B, 512))])
 wrap(C.convnet, "conv2_fwd", lambda a: [("conv2_fwd", slice(0, NFW))])
 wrap(C.convnet, "conv1_wgrad_slab2", lambda a: [("wgrad1_slab2/wgrad", slice(0, 7 * B)),
                                                  ("wgrad1_slab2/sums", slice(7 * B, 512))])
@@ -112,10 +120,17 @@ scaler = GradScaler()
 if not FORCED or m.defer_grad_sync_to(opt):  # as engine.TrainLoop
     m.set_slab_sink(opt)  # conv1's weight-gradient sums inside the optimizer launch
 crit = CrossEntropyLoss()
+# a device-resident uint8 set read through the step counter: the batch gather runs inside conv1
+NS = 8 * B
+imgs = torch.randint(0, 256, (NS, 28, 28), dtype=torch.uint8, device=dev)
+lbls = torch.randint(0, 10, (NS,), device=dev)
+order = torch.randperm(NS, device=dev)
+ctr = torch.zeros(2, dtype=torch.int32, device=dev)
 for it in range(4):
-    x = torch.rand(B, 1, 28, 28, device=dev).to(torch.bfloat16)
-    y = torch.randint(0, 10, (B,), device=dev)
+    x = torch.empty(B, 1, 28, 28, device=dev, dtype=torch.bfloat16)
+    y = torch.empty(B, dtype=torch.int64, device=dev)
     DeviceLoader.pair(x, y)
+    x._dpa_gather = (imgs, lbls, order, ctr, y, 1.0 / 255.0, 0.0)  # as DeviceLoader.fill_(defer=True)
     report.clear()
     loss = crit(m(x), y)
     opt.zero_grad(set_to_none=True)
