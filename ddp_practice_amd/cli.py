@@ -23,6 +23,11 @@ Additive flags (all optional; defaults reproduce the reference):
                                       layout) on a synthetic ImageNet-shaped set
                                       (--image-size, --num-classes; data/imagenet.py)
   --lr / --momentum / --weight-decay  SGD hyper-parameters (defaults: the reference's SGD(params, 1e-4))
+  --optimizer {sgd,adamw,adam}        adamw / adam: optim.AdamW / optim.Adam, one native launch per step whose
+                                      step count lives on the device, so it replays from the step graph
+                                      (optim/adamw.py); --betas B1,B2 and --adam-eps are theirs, --lr and
+                                      --weight-decay apply as given (set them: the defaults are SGD's),
+                                      --momentum is an error.  --impl torch: torch's optimizer of that name
   --lr-schedule {none,cosine,step}    cosine: --warmup-steps of linear warm-up, then cosine annealing over
                                       the run's remaining steps, stepped per step; step: x --lr-gamma at
                                       the --lr-milestones epochs, stepped per epoch.  On the native path
@@ -68,6 +73,9 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
     parser.add_argument("--lr", type=float, default=1e-4, help="SGD learning rate (the schedule's base rate)")
     parser.add_argument("--momentum", type=float, default=0.0)
     parser.add_argument("--weight-decay", type=float, default=0.0)
+    parser.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "adam"])
+    parser.add_argument("--betas", default="0.9,0.999", help="adamw / adam: beta1,beta2")
+    parser.add_argument("--adam-eps", type=float, default=1e-8, help="adamw / adam: eps")
     parser.add_argument("--lr-schedule", default="none", choices=["none", "cosine", "step"],
                         help="cosine: linear warm-up into cosine annealing, per step; step: MultiStepLR, per epoch")
     parser.add_argument("--warmup-steps", type=int, default=0, help="cosine: steps of linear warm-up")
@@ -147,7 +155,36 @@ WARMUP_START_FACTOR = 0.01  # --lr-schedule cosine: the warm-up's first rate, as
 def lr_flags_default(args) -> bool:
     """Every optimizer / schedule flag at its default: the run, and its checkpoint, are the reference's."""
     return (getattr(args, "lr", 1e-4) == 1e-4 and getattr(args, "momentum", 0.0) == 0.0
-            and getattr(args, "weight_decay", 0.0) == 0.0 and getattr(args, "lr_schedule", "none") == "none")
+            and getattr(args, "weight_decay", 0.0) == 0.0 and getattr(args, "lr_schedule", "none") == "none"
+            and getattr(args, "optimizer", "sgd") == "sgd")
+
+
+def optimizer_flags(args) -> tuple[str, dict]:
+    """(--optimizer, the constructor's keyword arguments) of a run; exits on flags that contradict each other."""
+    name = getattr(args, "optimizer", "sgd")
+    lr, wd = getattr(args, "lr", 1e-4), getattr(args, "weight_decay", 0.0)
+    if name == "sgd":
+        return name, dict(lr=lr, momentum=getattr(args, "momentum", 0.0), weight_decay=wd)
+    if getattr(args, "momentum", 0.0) != 0.0:
+        raise SystemExit(f"error: --momentum is SGD's; --optimizer {name} takes --betas B1,B2")
+    try:
+        b1, b2 = (float(x) for x in str(getattr(args, "betas", "0.9,0.999")).split(","))
+    except ValueError:
+        raise SystemExit(f"error: --betas expects B1,B2, not {args.betas!r}") from None
+    return name, dict(lr=lr, betas=(b1, b2), eps=getattr(args, "adam_eps", 1e-8), weight_decay=wd)
+
+
+def restore_optimizer(optimizer, saved: dict, name: str) -> None:
+    """Load a checkpoint's "optimizer" entry: the state only, the hyper-parameters are this run's flags.
+    A state of the other optimizer family is refused by name."""
+    kinds = {str(k) for st in saved.get("state", {}).values() for k in st}
+    is_adam = "exp_avg" in kinds
+    if kinds and is_adam != (name != "sgd"):
+        raise SystemExit(f"error: --resume: the checkpoint holds {'an Adam' if is_adam else 'an SGD'} optimizer "
+                         f"state ({', '.join(sorted(kinds))}), this run is --optimizer {name}")
+    osd = dict(saved)
+    osd["param_groups"] = optimizer.state_dict()["param_groups"]
+    optimizer.load_state_dict(osd)
 
 
 def scheduler_factory(args, total_steps: int):
@@ -261,7 +298,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     from ddp_practice_amd.engine import TrainLoop, evaluate
     from ddp_practice_amd.models import ConvNet
     from ddp_practice_amd.nn import CrossEntropyLoss
-    from ddp_practice_amd.optim import SGD
+    from ddp_practice_amd import optim as native_optim
     from ddp_practice_amd.utils import FaultInjector, Watchdog, set_tracing, trace_range
 
     phase("imports")
@@ -339,9 +376,9 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
         kw = {} if args.bucket_cap_mb is None else {"bucket_cap_mb": args.bucket_cap_mb}
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[dev.index] if gpu else None, **kw)
     criterion = (CrossEntropyLoss() if native else torch.nn.CrossEntropyLoss()).to(dev)
-    okw = dict(lr=getattr(args, "lr", 1e-4), momentum=getattr(args, "momentum", 0.0),
-               weight_decay=getattr(args, "weight_decay", 0.0))
-    optimizer = SGD(model.parameters(), **okw) if native else torch.optim.SGD(model.parameters(), **okw)
+    oname, okw = optimizer_flags(args)
+    ocls = getattr(native_optim if native else torch.optim, {"sgd": "SGD", "adamw": "AdamW", "adam": "Adam"}[oname])
+    optimizer = ocls(model.parameters(), **okw)
     phase("model")
 
     act_dtype = amp if (amp is not None and gpu) else torch.float32
@@ -395,10 +432,8 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
                 warnings.simplefilter("ignore")
                 for _ in range(pos):
                     scheduler.step()
-    if "optimizer" in resumed:  # the momentum buffers; the hyper-parameters are this run's flags
-        osd = dict(resumed["optimizer"])
-        osd["param_groups"] = optimizer.state_dict()["param_groups"]
-        optimizer.load_state_dict(osd)
+    if "optimizer" in resumed:  # momentum buffers / Adam moments and step count
+        restore_optimizer(optimizer, resumed["optimizer"], oname)
     # ResNet-50: hundreds of launches per step, one step per captured graph is enough
     loop = TrainLoop(model, criterion, optimizer, train_dloader, scaler, use_graph=native and not args.no_graph,
                      steps_per_graph=1 if resnet else 16, watchdog=watchdog, faults=faults, scheduler=scheduler,

@@ -329,6 +329,63 @@ __device__ __forceinline__ void sgd_rule4(f32x4& p, f32x4 g, f32x4& buf, bool fi
   }
 }
 
+// torch.optim.Adam / AdamW with ATen's capturable foreach rounding (torch/optim/adam.py
+// _multi_tensor_adam, capturable branch), spelled out in float32.  Contraction is off in both
+// functions: every fma below is one ATen's own kernels make (their `a + s * b` lines, built with
+// hipcc's default contraction), every other line rounds where the foreach op stores its result.
+struct AdamCoef {
+  float decay_mul;  // 1 - lr*wd (decoupled decay)
+  float wd;         // coupled decay
+  float w1;         // 1 - beta1: the lerp weight
+  float beta2, w2;  // w2 = 1 - beta2
+  float step_size;  // -lr / (1 - beta1^t)
+  float bc2_sqrt;   // sqrt(1 - beta2^t)
+  float eps;
+  int decoupled, maximize;
+};
+// The two bias-correction scalars of step t (t = the group's step word + 1).
+// inv_lr: (float)(1 / lr) of the host's double (a device-resident rate: 1.f / lr).
+__device__ __forceinline__ void adam_bias(float t, float inv_lr, float beta1, float beta2, AdamCoef& c) {
+#pragma clang fp contract(off)
+  const float b1 = powf(beta1, t) - 1.f;     // _foreach_pow(beta1, steps), _foreach_sub_(bc1, 1): two roundings;
+                                             // the sign stays (torch negates it with the update's)
+  const float b2 = -(powf(beta2, t) - 1.f);  // _foreach_pow, _foreach_sub_, _foreach_neg_ (exact)
+  c.step_size = 1.f / (b1 * inv_lr);         // _foreach_div_(bc1, lr), _foreach_reciprocal_: two roundings; ATen's
+                                             // division by a Python scalar is a product with its reciprocal,
+                                             // taken in double and rounded once (b1 / (float)lr is 1 ulp off
+                                             // at steps 2, 3, 10, 1000 with lr = 1e-3: profiles/adamw_vs_torch.txt)
+  c.bc2_sqrt = sqrtf(b2);                    // _foreach_sqrt_(bc2): one rounding
+}
+// One element: returns the new p; m (exp_avg) and v (exp_avg_sq) updated in place.
+__device__ __forceinline__ float adam_rule(float p, float g, float& m, float& v, const AdamCoef& c) {
+#pragma clang fp contract(off)
+  if (c.maximize) g = -g;                               // _foreach_neg(grads): exact
+  if (c.wd != 0.f) {
+    if (c.decoupled) p = p * c.decay_mul;               // _foreach_mul_(params, 1 - lr*wd): one rounding
+    else g = __builtin_fmaf(c.wd, p, g);                // _foreach_add(grads, params, alpha=wd): one fma
+  }
+  const float d = g - m;                                // _foreach_lerp_(exp_avgs, grads, 1 - beta1): ATen's
+  m = fabsf(c.w1) < 0.5f ? __builtin_fmaf(c.w1, d, m)   //   lerp rounds end - self, then one fma: self + w*diff
+                         : __builtin_fmaf(-d, 1.f - c.w1, g);  //   (w >= 0.5: end - diff*(1 - w))
+  const float vb = v * c.beta2;                         // _foreach_mul_(exp_avg_sqs, beta2): one rounding
+  v = __builtin_fmaf(c.w2, g * g, vb);                  // _foreach_addcmul_(v, g, g, 1 - beta2): g*g rounded, one fma
+  float den = sqrtf(v);                                 // _foreach_sqrt(exp_avg_sqs): one rounding
+  den = den / c.bc2_sqrt;                               // _foreach_div_(., bias_correction2_sqrt): one rounding
+  den = den + c.eps;                                    // _foreach_add_(., eps): one rounding
+  den = den / c.step_size;                              // _foreach_div_(., step_size): one rounding
+  return p + m / den;                                   // _foreach_addcdiv_(params, exp_avgs, .): m/den rounded, then the add
+}
+// four lanes of a granule
+__device__ __forceinline__ void adam_rule4(f32x4& p, f32x4 g, f32x4& m, f32x4& v, const AdamCoef& c) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float mj = m[j], vj = v[j];
+    p[j] = adam_rule(p[j], g[j], mj, vj, c);
+    m[j] = mj;
+    v[j] = vj;
+  }
+}
+
 // Can every workgroup of a `grid` x `threads` launch of `kernel` (dynamic LDS
 // `lds`) be resident on the current device at once?  Launches whose
 // workgroups wait on each other (grid barriers, in-kernel exchanges polled by

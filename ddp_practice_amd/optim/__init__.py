@@ -1,3 +1,4 @@
 """Optimizers (multi-tensor HIP kernels) and the device-resident learning-rate schedule."""
+from .adamw import Adam, AdamW  # noqa: F401
 from .lr import DeviceLR  # noqa: F401
 from .sgd import SGD  # noqa: F401
