@@ -33,6 +33,11 @@ Additive flags (all optional; defaults reproduce the reference):
                                       the --lr-milestones epochs, stepped per epoch.  On the native path
                                       the schedule lives on the device (optim/lr.py DeviceLR), so the
                                       graph-replayed steps follow it
+  --clip-grad-norm X                  clip the global gradient 2-norm to X before every update (0 = off).
+                                      adamw / adam: inside the optimizer's own step (optim/adamw.py
+                                      set_grad_clip); sgd: optim.clip_grad_norm_ between unscale_ and step;
+                                      --impl torch: torch.nn.utils.clip_grad_norm_.  --metrics-file rows
+                                      then carry grad_norm, the epoch's last step's norm
   --resume PATH [--start-epoch N]     load {"model"[, "scaler"][, "optimizer", "lr_scheduler"]} before
                                       training (the last two are written only with a non-default flag above)
   --watchdog-timeout S                abort + exit when no progress for S seconds (default at
@@ -81,6 +86,8 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
     parser.add_argument("--warmup-steps", type=int, default=0, help="cosine: steps of linear warm-up")
     parser.add_argument("--lr-milestones", default="", help="step: comma-separated epochs at which the rate drops")
     parser.add_argument("--lr-gamma", type=float, default=0.1, help="step: the factor of each drop")
+    parser.add_argument("--clip-grad-norm", type=float, default=0.0,
+                        help="clip the global gradient 2-norm to this before every update (0 = off)")
     parser.add_argument("--image-size", type=int, default=224, help="resnet50: synthetic image side")
     parser.add_argument("--num-classes", type=int, default=1000, help="resnet50: synthetic label count")
     if distributed:
@@ -156,7 +163,15 @@ def lr_flags_default(args) -> bool:
     """Every optimizer / schedule flag at its default: the run, and its checkpoint, are the reference's."""
     return (getattr(args, "lr", 1e-4) == 1e-4 and getattr(args, "momentum", 0.0) == 0.0
             and getattr(args, "weight_decay", 0.0) == 0.0 and getattr(args, "lr_schedule", "none") == "none"
-            and getattr(args, "optimizer", "sgd") == "sgd")
+            and getattr(args, "optimizer", "sgd") == "sgd" and getattr(args, "clip_grad_norm", 0.0) == 0.0)
+
+
+def clip_flag(args) -> float | None:
+    """--clip-grad-norm as TrainLoop's ``clip_grad_norm`` (0: None, off); exits on a negative value."""
+    v = float(getattr(args, "clip_grad_norm", 0.0) or 0.0)
+    if v < 0.0 or v != v:
+        raise SystemExit(f"error: --clip-grad-norm expects a norm >= 0 (0 = off), not {v}")
+    return v if v > 0.0 else None
 
 
 def optimizer_flags(args) -> tuple[str, dict]:
@@ -259,7 +274,7 @@ class _Metrics:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
-    def epoch(self, epoch: int, images: int, steps: int, scaler=None, lr=None):
+    def epoch(self, epoch: int, images: int, steps: int, scaler=None, lr=None, grad_norm=None):
         if self.path is None:
             return
         self._sync()
@@ -270,6 +285,8 @@ class _Metrics:
             rec["loss_scale"] = scaler.get_scale()
         if lr is not None:
             rec["lr"] = lr() if callable(lr) else lr  # one host read per epoch
+        if grad_norm is not None:
+            rec["grad_norm"] = float(grad_norm)  # the last step's, one host read per epoch
         with open(self.path, "a") as f:
             f.write(json.dumps(rec) + "\n")
         self.t0 = time.perf_counter()
@@ -290,6 +307,7 @@ def phase(name: str) -> None:
 def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None = None) -> None:
     """Build model/data/optimizer, train ``args.epochs`` epochs, test, save (rank 0)."""
     phase("run")
+    clip = clip_flag(args)
     import torch
 
     import ddp_practice_amd.distributed as dist
@@ -437,7 +455,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     # ResNet-50: hundreds of launches per step, one step per captured graph is enough
     loop = TrainLoop(model, criterion, optimizer, train_dloader, scaler, use_graph=native and not args.no_graph,
                      steps_per_graph=1 if resnet else 16, watchdog=watchdog, faults=faults, scheduler=scheduler,
-                     scheduler_interval=interval or "step")
+                     scheduler_interval=interval or "step", clip_grad_norm=clip)
     metrics = _Metrics(args.metrics_file, rank, world, dev)
     metrics.start()
     try:
@@ -450,7 +468,8 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
             check_health(comm, f"after epoch {epoch - args.start_epoch + 1}")
             metrics.epoch(epoch, len(train_dataset), len(train_dloader), scaler,
                           lr=(lambda: scheduler.get_last_lr()[0]) if scheduler is not None
-                          else optimizer.param_groups[0]["lr"])
+                          else optimizer.param_groups[0]["lr"],
+                          grad_norm=loop.grad_norm if clip is not None else None)
             phase(f"epoch {epoch}")
         if loop.graph_error is not None and rank == 0:
             print(f"[ddp_practice_amd] hipGraph capture failed, ran eagerly: {loop.graph_error!r}", file=sys.stderr)

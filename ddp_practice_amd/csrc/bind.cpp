@@ -23,6 +23,7 @@ void register_runtime(pybind11::module& m);
 void register_bn_nhwc(pybind11::module& m);
 void register_conv_igemm(pybind11::module& m);
 void register_adam(pybind11::module& m);
+void register_clip(pybind11::module& m);
 }
 
 // sha1 of the sources this library was built from (build.py generates it; _ext.py compares
@@ -63,4 +64,5 @@ PYBIND11_MODULE(_C, m) {
   dpa::register_bn_nhwc(m);
   dpa::register_conv_igemm(m);
   dpa::register_adam(m);
+  dpa::register_clip(m);
 }

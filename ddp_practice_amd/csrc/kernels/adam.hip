@@ -1,7 +1,9 @@
 // Adam / AdamW (optim/adamw.py): one launch updates every tensor of a param group.
 //   adam_step       : p, exp_avg, exp_avg_sq of up to LARGE_MAXT tensors by common.h adam_rule,
 //                     predicated on found_inf read ON DEVICE, the unscale folded in
-//                     (grad_scale), the rate optionally device-resident (lr_dev, optim/lr.py)
+//                     (grad_scale), the rate optionally device-resident (lr_dev, optim/lr.py),
+//                     the gradient optionally times a device-resident clipping coefficient
+//                     (clip_coef, csrc/kernels/clip.hip grad_norm)
 //   nonfinite_check : found_inf |= any(!isfinite(g)); reads the gradients, never writes them
 //   adam_table      : the device tensor table of a group of more than MAXT tensors
 //
@@ -18,30 +20,11 @@
 // in fixed chunks of ADAM_THR * U granules that the workgroups walk grid-stride, so ResNet-50's
 // 161 mostly tiny tensors do not cost a workgroup each.  The last granule of a tensor whose
 // numel is not a multiple of 4, and every granule of a tensor with a pointer that is not
-// 16-byte aligned, moves per element.
-#include <cstdlib>
-#include "common.h"
-#include "kernels/amp_step.h"
-
-#include <vector>
+// 16-byte aligned, moves per element (kernels/multi_tensor.h, shared with clip.hip).
+#include "kernels/multi_tensor.h"
 
 namespace dpa {
 namespace adam {
-
-using opt::MAXT;
-constexpr int LARGE_MAXT = 512;  // == optim.hip's: one bound for every tensor table of the package
-constexpr int ADAM_THR = 256;
-
-// <= MAXT tensors by value; off: prefix sum of granules
-struct AdamList {
-  int n;
-  long long off[MAXT + 1];
-  long long numel[MAXT];
-  float* p[MAXT];
-  float* g[MAXT];
-  float* m[MAXT];
-  float* v[MAXT];
-};
 
 // Device table (int64): [0] n, [1] total granules, then off[n+1] | numel[n] | p[n] | g[n] | m[n] | v[n]
 __global__ void __launch_bounds__(64) adam_table_kernel(int64_t* __restrict__ table, int n, int s, int e, AdamList c,
@@ -62,80 +45,6 @@ __global__ void __launch_bounds__(64) adam_table_kernel(int64_t* __restrict__ ta
   }
 }
 
-// The tensor list of a launch in LDS, from the by-value list or the device table.
-struct Staged {
-  long long off[LARGE_MAXT + 1];
-  long long numel[LARGE_MAXT];
-  float* p[LARGE_MAXT];
-  float* g[LARGE_MAXT];
-  float* m[LARGE_MAXT];
-  float* v[LARGE_MAXT];
-  unsigned char vec[LARGE_MAXT];  // all four pointers 16-byte aligned: granules move as one access
-};
-
-template <bool TABLE>
-__device__ __forceinline__ void stage(Staged& S, const AdamList& L, const int64_t* __restrict__ table, int& n,
-                                      long long& total, bool grads_only) {
-  const int tid = threadIdx.x;
-  if (TABLE) {
-    n = (int)table[0];
-    total = table[1];
-    const int64_t* off = table + 2;
-    for (int t = tid; t <= n; t += ADAM_THR) S.off[t] = off[t];
-    for (int t = tid; t < n; t += ADAM_THR) {
-      S.numel[t] = off[n + 1 + t];
-      const int64_t p = off[2 * n + 1 + t], g = off[3 * n + 1 + t], m = off[4 * n + 1 + t], v = off[5 * n + 1 + t];
-      S.p[t] = reinterpret_cast<float*>(p);
-      S.g[t] = reinterpret_cast<float*>(g);
-      S.m[t] = reinterpret_cast<float*>(m);
-      S.v[t] = reinterpret_cast<float*>(v);
-      S.vec[t] = ((grads_only ? g : (p | g | m | v)) & 15) == 0;
-    }
-  } else {
-    n = L.n;
-    total = L.off[L.n];
-    for (int t = tid; t <= n; t += ADAM_THR) S.off[t] = L.off[t];
-    for (int t = tid; t < n; t += ADAM_THR) {
-      S.numel[t] = L.numel[t];
-      S.p[t] = L.p[t];
-      S.g[t] = L.g[t];
-      S.m[t] = L.m[t];
-      S.v[t] = L.v[t];
-      const uintptr_t a = reinterpret_cast<uintptr_t>(L.g[t]);
-      const uintptr_t b = reinterpret_cast<uintptr_t>(L.p[t]) | reinterpret_cast<uintptr_t>(L.m[t]) |
-                          reinterpret_cast<uintptr_t>(L.v[t]);
-      S.vec[t] = ((grads_only ? a : (a | b)) & 15) == 0;
-    }
-  }
-}
-
-// One granule: `rem` = elements from p to the tensor's end (>= 1); lanes past it read 0 and
-// are not written.
-template <bool NT>
-__device__ __forceinline__ f32x4 load4(const float* p, long long rem, bool vec) {
-  if (rem >= 4 && vec) {
-    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-    return *reinterpret_cast<const f32x4*>(p);
-  }
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (j < rem) v[j] = p[j];
-  return v;
-}
-__device__ __forceinline__ void store4(float* p, long long rem, bool vec, f32x4 v) {
-  if (rem >= 4 && vec) { *reinterpret_cast<f32x4*>(p) = v; return; }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (j < rem) p[j] = v[j];
-}
-
-// g * (1/scale), rounded on its own: what unscale_check_kernel (optim.hip) stores
-__device__ __forceinline__ f32x4 unscaled(f32x4 g, float gs) {
-#pragma clang fp contract(off)
-  return g * gs;
-}
-
 // 1 - lr*wd from a device-resident rate: the product rounded, then the difference
 __device__ __forceinline__ float decay_of(float lr, float wd) {
 #pragma clang fp contract(off)
@@ -150,12 +59,16 @@ struct AdamHyper {
   int decoupled, maximize;
 };
 
-// U granules per lane and chunk; NT: exp_avg / exp_avg_sq loads non-temporal
-template <bool TABLE, int U, bool NT>
+// U granules per lane and chunk; NT: exp_avg / exp_avg_sq loads non-temporal; CLIP: the unscaled
+// gradient times clip_coef[0], the two products rounded one after the other -- what unscale_
+// followed by clip.scale_ stores.  A template flag, not a null test, and the word is the last
+// argument, behind `grid`: the unclipped instantiations are instruction for instruction the
+// kernels measured in profiles/adamw_step_ab.txt (no argument of theirs moved).
+template <bool TABLE, int U, bool NT, bool CLIP>
 __global__ void __launch_bounds__(ADAM_THR)
 adam_kernel(AdamList L, const int64_t* __restrict__ table, float* step_word, unsigned* ticket, AdamHyper h,
             const float* __restrict__ found_inf, const float* __restrict__ grad_scale,
-            const float* __restrict__ lr_dev, int grid) {
+            const float* __restrict__ lr_dev, int grid, const float* __restrict__ clip_coef) {
   __shared__ Staged S;
   const int tid = threadIdx.x;
   // the step count first: an atomic load, so it is made once, here, before this workgroup's
@@ -171,6 +84,8 @@ adam_kernel(AdamList L, const int64_t* __restrict__ table, float* step_word, uns
   // ticket is taken, p / m / v and the step word stay as they are
   if (found_inf != nullptr && found_inf[0] != 0.f) return;
   const float gs = grad_scale != nullptr ? 1.f / grad_scale[0] : 1.f;
+  float cf = 1.f;  // a skipped step has returned above: whatever the word holds then is not read
+  if constexpr (CLIP) cf = clip_coef[0];
   int n;
   long long total;
   stage<TABLE>(S, L, table, n, total, false);
@@ -206,7 +121,9 @@ adam_kernel(AdamList L, const int64_t* __restrict__ table, float* step_word, uns
       const long long o = (base + (long long)u * ADAM_THR - S.off[tu]) * 4, rem = S.numel[tu] - o;
       const bool vec = S.vec[tu];
       f32x4 pn = pv[u], mn = mv[u], vn = vv[u];
-      adam_rule4(pn, unscaled(gv[u], gs), mn, vn, c);
+      f32x4 gu = unscaled(gv[u], gs);
+      if constexpr (CLIP) gu = unscaled(gu, cf);
+      adam_rule4(pn, gu, mn, vn, c);
       store4(S.m[tu] + o, rem, vec, mn);
       store4(S.v[tu] + o, rem, vec, vn);
       store4(S.p[tu] + o, rem, vec, pn);
@@ -260,58 +177,6 @@ nonfinite_check_kernel(AdamList L, const int64_t* __restrict__ table, float* __r
   if (__any(bad) && (tid & 63) == 0) found_inf[0] = 1.f;  // every writer stores the same value
 }
 
-static void check_f32(const at::Tensor& t) {
-  DPA_CHECK_INPUT(t);
-  TORCH_CHECK(t.scalar_type() == at::kFloat, "optimizer tensors must be f32");
-}
-
-static const float* opt_word(const c10::optional<at::Tensor>& w, const at::Tensor& like, const char* what) {
-  if (!w.has_value()) return nullptr;
-  check_f32(*w);
-  TORCH_CHECK(w->numel() == 1 && w->device() == like.device(), what, ": one f32 word on the parameters' device");
-  return w->data_ptr<float>();
-}
-
-// Workgroups of a launch over `total` granules in chunks of `chunk`: one per chunk up to 8 per CU
-static int grid_cap() {
-  static const int cap = [] {
-    int dev = 0, cus = 0;
-    DPA_CHECK_HIP(hipGetDevice(&dev));
-    DPA_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    return std::max(1, resident_cus(cus)) * 8;
-  }();
-  return cap;
-}
-static int grid_for(long long total, long long chunk) {
-  return (int)std::max<long long>(1, std::min<long long>((total + chunk - 1) / chunk, grid_cap()));
-}
-
-// the by-value list of tensors [s, e); lists other than grads may be empty (the check)
-static AdamList list_of(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads,
-                        const std::vector<at::Tensor>& ms, const std::vector<at::Tensor>& vs, size_t s, size_t e) {
-  AdamList L{};
-  L.n = (int)(e - s);
-  L.off[0] = 0;
-  for (size_t i = s; i < e; ++i) {
-    const int k = (int)(i - s);
-    check_f32(grads[i]);
-    L.numel[k] = grads[i].numel();
-    L.g[k] = grads[i].data_ptr<float>();
-    if (!params.empty()) {
-      check_f32(params[i]); check_f32(ms[i]); check_f32(vs[i]);
-      TORCH_CHECK(params[i].numel() == L.numel[k] && ms[i].numel() == L.numel[k] && vs[i].numel() == L.numel[k],
-                  "adam: a parameter, its gradient and its state differ in size");
-      TORCH_CHECK(params[i].device() == grads[i].device() && ms[i].device() == grads[i].device() &&
-                      vs[i].device() == grads[i].device(), "adam: tensors on one device");
-      L.p[k] = params[i].data_ptr<float>();
-      L.m[k] = ms[i].data_ptr<float>();
-      L.v[k] = vs[i].data_ptr<float>();
-    }
-    L.off[k + 1] = L.off[k] + (L.numel[k] + 3) / 4;
-  }
-  return L;
-}
-
 // Device table of a group of up to LARGE_MAXT tensors: written by by-value upload launches
 // (one per MAXT tensors), so building it is stream-ordered and graph-capturable.
 at::Tensor adam_table(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, std::vector<at::Tensor> ms,
@@ -334,11 +199,6 @@ at::Tensor adam_table(std::vector<at::Tensor> params, std::vector<at::Tensor> gr
   return table;
 }
 
-static void check_table(const at::Tensor& table) {
-  DPA_CHECK_INPUT(table);
-  TORCH_CHECK(table.scalar_type() == at::kLong && table.numel() >= 9, "adam: table from adam_table");
-}
-
 // Kernel variant, measured in profiles/adamw_step_ab.txt: non-temporal exp_avg / exp_avg_sq loads
 // (ResNet-50's set: 155.0 against 165.3 us at 2 granules per lane; the ConvNet's: no difference),
 // and the granules per lane and chunk: 2 once that fills the grid (ResNet-50: 155.0 us, 1: 156.7,
@@ -355,7 +215,8 @@ void adam_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, st
                std::vector<at::Tensor> vs, at::Tensor step_word, double lr, double beta1, double beta2, double eps,
                double wd, bool decoupled, bool maximize, c10::optional<at::Tensor> found_inf,
                c10::optional<at::Tensor> grad_scale, c10::optional<at::Tensor> lr_dev,
-               c10::optional<at::Tensor> ticket, c10::optional<at::Tensor> table, int64_t total_granules) {
+               c10::optional<at::Tensor> ticket, c10::optional<at::Tensor> table, int64_t total_granules,
+               c10::optional<at::Tensor> clip_coef) {
   check_f32(step_word);
   TORCH_CHECK(step_word.numel() == 1, "adam_step: step_word is one f32 word");
   unsigned* tk = nullptr;  // None: the count is not advanced (measurements only)
@@ -368,6 +229,7 @@ void adam_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, st
   const float* fi = opt_word(found_inf, step_word, "found_inf");
   const float* gsp = opt_word(grad_scale, step_word, "grad_scale");
   const float* lrp = opt_word(lr_dev, step_word, "lr_dev");
+  const float* ccp = opt_word(clip_coef, step_word, "clip_coef");
   AdamList L{};
   const int64_t* tab = nullptr;
   long long total;
@@ -391,22 +253,25 @@ void adam_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads, st
   auto launch = [&](auto kern, int u) {
     const int grid = grid_for(total, (long long)ADAM_THR * u);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(ADAM_THR), 0, cur_stream(), L, tab, step_word.data_ptr<float>(), tk, h,
-                       fi, gsp, lrp, grid);
+                       fi, gsp, lrp, grid, ccp);
   };
   const int gu = g_u != 0 ? g_u : (total >= (long long)grid_cap() * ADAM_THR * 2 ? 2 : 1);
-  auto pick = [&](auto table_c) {
-    constexpr bool T = decltype(table_c)::value;
+  auto pick = [&](auto table_c, auto clip_c) {
+    constexpr bool T = decltype(table_c)::value, CL = decltype(clip_c)::value;
     if (g_nt) {
-      if (gu == 1) launch(adam_kernel<T, 1, true>, 1);
-      else if (gu == 2) launch(adam_kernel<T, 2, true>, 2);
-      else launch(adam_kernel<T, 4, true>, 4);
+      if (gu == 1) launch(adam_kernel<T, 1, true, CL>, 1);
+      else if (gu == 2) launch(adam_kernel<T, 2, true, CL>, 2);
+      else launch(adam_kernel<T, 4, true, CL>, 4);
     } else {
-      if (gu == 1) launch(adam_kernel<T, 1, false>, 1);
-      else if (gu == 2) launch(adam_kernel<T, 2, false>, 2);
-      else launch(adam_kernel<T, 4, false>, 4);
+      if (gu == 1) launch(adam_kernel<T, 1, false, CL>, 1);
+      else if (gu == 2) launch(adam_kernel<T, 2, false, CL>, 2);
+      else launch(adam_kernel<T, 4, false, CL>, 4);
     }
   };
-  if (tab != nullptr) pick(std::true_type{}); else pick(std::false_type{});
+  auto pick_clip = [&](auto table_c) {
+    if (ccp != nullptr) pick(table_c, std::true_type{}); else pick(table_c, std::false_type{});
+  };
+  if (tab != nullptr) pick_clip(std::true_type{}); else pick_clip(std::false_type{});
   DPA_CHECK_LAUNCH();
 }
 
@@ -449,7 +314,8 @@ void register_adam(pybind11::module& m) {
         py::arg("exp_avg_sqs"), py::arg("step_word"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"),
         py::arg("eps"), py::arg("weight_decay"), py::arg("decoupled"), py::arg("maximize"),
         py::arg("found_inf") = py::none(), py::arg("grad_scale") = py::none(), py::arg("lr_dev") = py::none(),
-        py::kw_only(), py::arg("ticket"), py::arg("table") = py::none(), py::arg("total_granules") = 0);
+        py::kw_only(), py::arg("ticket"), py::arg("table") = py::none(), py::arg("total_granules") = 0,
+        py::arg("clip_coef") = py::none());
   s.def("nonfinite_check", &adam::nonfinite_check, py::arg("grads"), py::arg("found_inf"),
         py::arg("table") = py::none(), py::arg("total_granules") = 0);
   s.def("adam_table", &adam::adam_table, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),

@@ -70,7 +70,7 @@ class TrainLoop:
 
     def __init__(self, model, criterion, optimizer, loader: DeviceLoader, scaler=None, use_graph: bool = True,
                  steps_per_graph: int = 16, watchdog=None, faults=None, scheduler=None,
-                 scheduler_interval: str = "step"):
+                 scheduler_interval: str = "step", clip_grad_norm: float | None = None):
         self.model = model
         self.criterion = criterion
         self.optimizer = optimizer
@@ -107,11 +107,51 @@ class TrainLoop:
         elif fused and hasattr(model, "set_slab_sink"):
             # no DDP: the fused step also sums the conv1 weight-gradient slab (models/convnet.py)
             model.set_slab_sink(optimizer)
+        # clip_grad_norm: the global gradient norm is clipped to it before every update.  The
+        # native Adam family does it inside its own step (optim/adamw.py set_grad_clip: nothing
+        # changes in _step); optim.SGD through optim.clip_grad_norm_ between unscale_ and step
+        # (its unfused route); any other optimizer through torch's function, so the --impl
+        # torch runs stay an independent reference
+        self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
+        self._clip_mode = None
+        self._norm_words = None  # [norm, coefficient] of the last step (the two non-fused routes)
+        if self.clip_grad_norm is not None:
+            if not self.clip_grad_norm > 0.0:
+                raise ValueError(f"clip_grad_norm must be positive, not {clip_grad_norm!r}")
+            from .optim import SGD
+
+            if hasattr(optimizer, "set_grad_clip"):
+                optimizer.set_grad_clip(self.clip_grad_norm)
+                self._clip_mode = "fused"
+            else:
+                self._clip_mode = "native" if isinstance(optimizer, SGD) else "torch"
+                self._norm_words = torch.tensor([0.0, 1.0], dtype=torch.float32, device=self.device)
         self.global_step = 0
         # the model's first kernel gathers the batch itself (no gather launch per step)
         from .data.loader import accepts_deferred
 
         self._defer = accepts_deferred(model, self.images)
+
+    @property
+    def grad_norm(self):
+        """The last step's total gradient norm before clipping (a 0-d device tensor; None
+        without ``clip_grad_norm``)."""
+        if self._clip_mode == "fused":
+            return self.optimizer.grad_norm
+        return None if self._norm_words is None else self._norm_words[0]
+
+    def _clip(self):
+        """Clip the (unscaled, complete) gradients in place; the norm goes to ``_norm_words``."""
+        params = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
+        if self._clip_mode == "native":
+            from .optim import clip as K
+
+            grads = [p.grad for p in params]
+            if K.native_ok(grads):
+                K.clip_grads_(grads, self.clip_grad_norm, self._norm_words)
+                return
+        norm = torch.nn.utils.clip_grad_norm_(params, self.clip_grad_norm)
+        self._norm_words[0].copy_(norm)
 
     # -- one step on the static buffers (what gets captured)
     def _step(self, images=None, labels=None, fill=True, before_update=None):
@@ -132,6 +172,9 @@ class TrainLoop:
                     flush()  # the hook reads .grad
                 before_update()
             with trace_range("optimizer"):
+                if self._norm_words is not None:
+                    self.scaler.unscale_(self.optimizer)  # (the native scaler's flushes first)
+                    self._clip()
                 self.scaler.step(self.optimizer)
                 self.scaler.update()
         else:
@@ -140,6 +183,11 @@ class TrainLoop:
             if before_update is not None:
                 before_update()
             with trace_range("optimizer"):
+                if self._norm_words is not None:
+                    flush = getattr(self.optimizer, "_flush_deferred", None)
+                    if flush is not None:
+                        flush()
+                    self._clip()
                 self.optimizer.step()
         if self.scheduler is not None and self.scheduler_interval == "step":
             self.scheduler.step()

@@ -1,4 +1,5 @@
-"""Optimizers (multi-tensor HIP kernels) and the device-resident learning-rate schedule."""
+"""Optimizers (multi-tensor HIP kernels), gradient clipping and the device-resident learning-rate schedule."""
 from .adamw import Adam, AdamW  # noqa: F401
+from .clip import clip_grad_norm_  # noqa: F401
 from .lr import DeviceLR  # noqa: F401
 from .sgd import SGD  # noqa: F401

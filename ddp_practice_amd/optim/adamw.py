@@ -12,7 +12,15 @@ hipGraph (``engine.TrainLoop``):
   launch reads the word and the launch's last workgroup advances it;
 * ``found_inf`` is read on the device (``supports_device_found_inf``): a skipped step leaves
   the parameters, both moments and the step word untouched, bit for bit;
-* the learning rate is read from the ``optim.DeviceLR`` word when one is attached.
+* the learning rate is read from the ``optim.DeviceLR`` word when one is attached;
+* ``set_grad_clip(max_norm)`` clips the global gradient norm inside the step: one read-only
+  norm launch over the gradients of every param group (optim/clip.py; under ``GradScaler`` it
+  takes the place of the non-finite check, whose pass over the gradients it shares), and the
+  update multiplies each gradient by the coefficient word that launch left on the device.
+  The gradients are not written, and the result is bitwise what ``unscale_()`` ->
+  ``optim.clip_grad_norm_`` -> ``step()`` gives.  The fused route covers at most
+  ``LARGE_MAXT`` gradients in total; beyond that ``GradScaler`` takes its explicit route and
+  the clip is torch's function.
 
 The one deviation from torch: **the parameters of a group share one step count.**
 ``state[p]["step"]`` is the same 0-d float32 tensor for every parameter of a group (so
@@ -80,6 +88,51 @@ class Adam(Optimizer):
         for gi, group in enumerate(self.param_groups):
             if group["params"] and group["params"][0].is_cuda and not _capturing(group["params"][0].device):
                 self._ticket(gi, group["params"][0].device)
+        self._clip: float | None = None
+
+    # ------------------------------------------------------------------ clipping
+    def set_grad_clip(self, max_norm: float | None) -> None:
+        """Clip the global 2-norm of the gradients of all param groups to ``max_norm`` inside
+        every step (None: off).  An attribute, not a param-group key: ``state_dict()`` keeps
+        loading into ``torch.optim.AdamW``."""
+        if max_norm is not None:
+            max_norm = float(max_norm)
+            if not max_norm > 0.0:
+                raise ValueError(f"Invalid max_norm: {max_norm}")
+        self._clip = max_norm
+
+    @property
+    def grad_norm(self) -> torch.Tensor | None:
+        """The last clipped step's total gradient norm: a 0-d float32 tensor on the device (no
+        host sync; a step that found_inf skipped leaves the non-finite norm it saw)."""
+        w = self.__dict__.get("_clip_out")
+        return None if w is None else w[0]
+
+    def _clip_words(self, dev: torch.device) -> torch.Tensor:
+        w = self.__dict__.get("_clip_out")
+        if w is None or w.device != dev or w.numel() != 2:
+            if _capturing(dev):
+                raise RuntimeError(_NEED_EAGER.format(type(self).__name__))
+            w = self._clip_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+        return w
+
+    def _clip_native(self, groups) -> bool:
+        n = sum(len(g[1]) for g in groups)
+        devs = {p.device for g in groups for p in g[1]}
+        return (0 < n <= _load_ext().adam.LARGE_MAXT and len(devs) == 1
+                and all(self._native(*g[1:5]) for g in groups if g[1]))
+
+    def _norm_launch(self, groups, grad_scale=None, found_inf=None) -> torch.Tensor:
+        """One norm launch over the gradients of every group, in group order; returns the
+        coefficient word the updates read."""
+        from . import clip as K
+
+        grads = [g for grp in groups for g in grp[2]]
+        out = self._clip_words(grads[0].device)
+        K.grad_norm_into(grads, self._clip, out, grad_scale, found_inf,
+                         self.__dict__.setdefault("_clip_tables", {}), self.__dict__.setdefault("_tables_pinned", []),
+                         type(self).__name__)
+        return out[1:2]
 
     # ------------------------------------------------------------------ state
     def _ticket(self, gi: int, dev: torch.device) -> torch.Tensor:
@@ -216,8 +269,10 @@ class Adam(Optimizer):
         total = sum((p.numel() + 3) // 4 for p in params)
         return ([], [], [], []), {"table": self._table(gi, params, grads, ms, vs), "total_granules": total}
 
-    def _native_step(self, gi, group, params, grads, ms, vs, word, found_inf, grad_scale):
+    def _native_step(self, gi, group, params, grads, ms, vs, word, found_inf, grad_scale, clip_coef=None):
         lists, kw = self._launch_args(gi, params, grads, ms, vs)
+        if clip_coef is not None:
+            kw["clip_coef"] = clip_coef
         b1, b2 = group["betas"]
         _load_ext().adam.adam_step(*lists, word, group["lr"], b1, b2, group["eps"], group["weight_decay"],
                                    group["decoupled_weight_decay"], group["maximize"], found_inf, grad_scale,
@@ -230,11 +285,19 @@ class Adam(Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for gi, (group, params, grads, ms, vs, word) in enumerate(self._collect()):
+        groups = self._collect()
+        coef = None
+        if self.__dict__.get("_clip") is not None and any(g[1] for g in groups):
+            if self._clip_native(groups):
+                coef = self._norm_launch(groups)
+            else:  # torch's clip, in place, as the update below is torch's
+                self._clip_out = torch.nn.utils.clip_grad_norm_(
+                    [p for g in groups for p in g[1]], self._clip).detach().reshape(1)
+        for gi, (group, params, grads, ms, vs, word) in enumerate(groups):
             if not params:
                 continue
             if self._native(params, grads, ms, vs):
-                self._native_step(gi, group, params, grads, ms, vs, word, found_inf, None)
+                self._native_step(gi, group, params, grads, ms, vs, word, found_inf, None, coef)
             else:
                 if found_inf is not None and bool(found_inf.item()):
                     continue
@@ -263,10 +326,14 @@ class Adam(Optimizer):
         """GradScaler.step as three barrier-free launches (``fused_amp_step``): every group on
         the native kernel, and its state in place if a capture is under way."""
         seen = False
+        total = 0
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
+            total += len(ps)
+            if self.__dict__.get("_clip") is not None and total > _load_ext().adam.LARGE_MAXT:
+                return False  # one norm launch covers LARGE_MAXT gradients: the explicit route
             if len(ps) != len(group["params"]) or len(ps) > _load_ext().adam.LARGE_MAXT:
                 return False
             if not all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and not p.grad.is_sparse
@@ -281,15 +348,21 @@ class Adam(Optimizer):
         a read-only non-finite check of the (still scaled) gradients into ``found_inf``, the
         update with the unscale folded in (``grad_scale``; the gradients are left as they are),
         and GradScaler's own ``update_scale``, which also re-arms ``found_inf``.  The check only
-        ever sets ``found_inf``: it must be zero on entry, as GradScaler keeps it."""
+        ever sets ``found_inf``: it must be zero on entry, as GradScaler keeps it.  With a clip
+        set the check is the norm launch's (same pass, same word) and the update also reads
+        the coefficient; a skipped step ignores whatever that word holds."""
         self._flush_deferred()
         C = _load_ext()
         groups = [(gi, g) for gi, g in enumerate(self._collect()) if g[1]]
+        coef = None
+        if self.__dict__.get("_clip") is not None and groups:
+            coef = self._norm_launch([g for _, g in groups], scale, found_inf)
+        else:
+            for gi, (group, params, grads, ms, vs, word) in groups:
+                lists, kw = self._launch_args(gi, params, grads, ms, vs)
+                C.adam.nonfinite_check(lists[1], found_inf, **kw)
         for gi, (group, params, grads, ms, vs, word) in groups:
-            lists, kw = self._launch_args(gi, params, grads, ms, vs)
-            C.adam.nonfinite_check(lists[1], found_inf, **kw)
-        for gi, (group, params, grads, ms, vs, word) in groups:
-            self._native_step(gi, group, params, grads, ms, vs, word, found_inf, scale)
+            self._native_step(gi, group, params, grads, ms, vs, word, found_inf, scale, coef)
         C.optim.update_scale(scale, tracker, found_inf, growth, backoff, interval)
 
 
