@@ -38,8 +38,15 @@ Additive flags (all optional; defaults reproduce the reference):
                                       set_grad_clip); sgd: optim.clip_grad_norm_ between unscale_ and step;
                                       --impl torch: torch.nn.utils.clip_grad_norm_.  --metrics-file rows
                                       then carry grad_norm, the epoch's last step's norm
-  --resume PATH [--start-epoch N]     load {"model"[, "scaler"][, "optimizer", "lr_scheduler"]} before
-                                      training (the last two are written only with a non-default flag above)
+  --ema-decay D                       keep an exponential moving average of the weights (0 = off): optim.EMA,
+                                      one launch per step whose update count lives on the device, captured
+                                      with the step (optim/ema.py); --impl torch: torch's AveragedModel.
+                                      --ema-buffers averages the float buffers too (else they are copied),
+                                      --ema-warmup (native only) uses min(D, (1 + n) / (10 + n)) at update n.
+                                      ``EMA accuracy is xx.xx%`` follows the accuracy line, the checkpoint
+                                      gains "ema" (AveragedModel's layout), --metrics-file rows ema_updates
+  --resume PATH [--start-epoch N]     load {"model"[, "scaler"][, "optimizer", "lr_scheduler"][, "ema"]} before
+                                      training (the last three are written only with a non-default flag above)
   --watchdog-timeout S                abort + exit when no progress for S seconds (default at
                                       world size > 1: 600, torch's ProcessGroupNCCL default; 0 = off)
   --profile                           roctx ranges (rocprofv3 --marker-trace)
@@ -88,6 +95,11 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
     parser.add_argument("--lr-gamma", type=float, default=0.1, help="step: the factor of each drop")
     parser.add_argument("--clip-grad-norm", type=float, default=0.0,
                         help="clip the global gradient 2-norm to this before every update (0 = off)")
+    parser.add_argument("--ema-decay", type=float, default=0.0,
+                        help="keep an exponential moving average of the weights with this decay (0 = off)")
+    parser.add_argument("--ema-buffers", action="store_true", help="average the float buffers too (else: copied)")
+    parser.add_argument("--ema-warmup", action="store_true",
+                        help="update n uses min(decay, (1 + n) / (10 + n)); native route only")
     parser.add_argument("--image-size", type=int, default=224, help="resnet50: synthetic image side")
     parser.add_argument("--num-classes", type=int, default=1000, help="resnet50: synthetic label count")
     if distributed:
@@ -172,6 +184,22 @@ def clip_flag(args) -> float | None:
     if v < 0.0 or v != v:
         raise SystemExit(f"error: --clip-grad-norm expects a norm >= 0 (0 = off), not {v}")
     return v if v > 0.0 else None
+
+
+def ema_flags(args) -> dict | None:
+    """--ema-decay / --ema-buffers / --ema-warmup as optim.EMA's keyword arguments (decay 0: None,
+    off); exits on a decay outside [0, 1) and on flags that contradict each other."""
+    d = float(getattr(args, "ema_decay", 0.0) or 0.0)
+    buffers, warmup = bool(getattr(args, "ema_buffers", False)), bool(getattr(args, "ema_warmup", False))
+    if not 0.0 <= d < 1.0:
+        raise SystemExit(f"error: --ema-decay expects a decay in [0, 1) (0 = off), not {d}")
+    if d == 0.0:
+        if buffers or warmup:
+            raise SystemExit("error: --ema-buffers / --ema-warmup need --ema-decay")
+        return None
+    if warmup and getattr(args, "impl", "native") == "torch":
+        raise SystemExit("error: --ema-warmup is optim.EMA's; torch's AveragedModel (--impl torch) has no such mode")
+    return dict(decay=d, use_buffers=buffers, warmup=warmup)
 
 
 def optimizer_flags(args) -> tuple[str, dict]:
@@ -274,7 +302,7 @@ class _Metrics:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
-    def epoch(self, epoch: int, images: int, steps: int, scaler=None, lr=None, grad_norm=None):
+    def epoch(self, epoch: int, images: int, steps: int, scaler=None, lr=None, grad_norm=None, ema_updates=None):
         if self.path is None:
             return
         self._sync()
@@ -287,6 +315,8 @@ class _Metrics:
             rec["lr"] = lr() if callable(lr) else lr  # one host read per epoch
         if grad_norm is not None:
             rec["grad_norm"] = float(grad_norm)  # the last step's, one host read per epoch
+        if ema_updates is not None:
+            rec["ema_updates"] = int(ema_updates)  # n_averaged, one host read per epoch
         with open(self.path, "a") as f:
             f.write(json.dumps(rec) + "\n")
         self.t0 = time.perf_counter()
@@ -308,6 +338,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     """Build model/data/optimizer, train ``args.epochs`` epochs, test, save (rank 0)."""
     phase("run")
     clip = clip_flag(args)
+    ema_kw = ema_flags(args)
     import torch
 
     import ddp_practice_amd.distributed as dist
@@ -452,10 +483,25 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
                     scheduler.step()
     if "optimizer" in resumed:  # momentum buffers / Adam moments and step count
         restore_optimizer(optimizer, resumed["optimizer"], oname)
+    # The weight average: optim.EMA on the native route (one launch, captured with the step);
+    # --impl torch keeps torch's AveragedModel, an independent reference.  Both start from the
+    # resumed weights; a checkpoint's "ema" continues the average and its count.
+    ema = None
+    if ema_kw is not None:
+        if native:
+            ema = native_optim.EMA(model, **ema_kw)
+        else:
+            from torch.optim.swa_utils import AveragedModel, get_ema_multi_avg_fn
+
+            plain = model.module if distributed else model
+            ema = AveragedModel(plain, multi_avg_fn=get_ema_multi_avg_fn(ema_kw["decay"]),
+                                use_buffers=ema_kw["use_buffers"])
+        if "ema" in resumed:
+            ema.load_state_dict(resumed["ema"])
     # ResNet-50: hundreds of launches per step, one step per captured graph is enough
     loop = TrainLoop(model, criterion, optimizer, train_dloader, scaler, use_graph=native and not args.no_graph,
                      steps_per_graph=1 if resnet else 16, watchdog=watchdog, faults=faults, scheduler=scheduler,
-                     scheduler_interval=interval or "step", clip_grad_norm=clip)
+                     scheduler_interval=interval or "step", clip_grad_norm=clip, ema=ema)
     metrics = _Metrics(args.metrics_file, rank, world, dev)
     metrics.start()
     try:
@@ -469,7 +515,8 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
             metrics.epoch(epoch, len(train_dataset), len(train_dloader), scaler,
                           lr=(lambda: scheduler.get_last_lr()[0]) if scheduler is not None
                           else optimizer.param_groups[0]["lr"],
-                          grad_norm=loop.grad_norm if clip is not None else None)
+                          grad_norm=loop.grad_norm if clip is not None else None,
+                          ema_updates=ema.n_averaged if ema is not None else None)
             phase(f"epoch {epoch}")
         if loop.graph_error is not None and rank == 0:
             print(f"[ddp_practice_amd] hipGraph capture failed, ran eagerly: {loop.graph_error!r}", file=sys.stderr)
@@ -477,14 +524,25 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
             print("begin testing", flush=True)
         with trace_range("evaluate"):
             correct, size = evaluate(model, test_dloader, comm=comm, dst=0, native=native)
+        if ema is not None:  # the same evaluation with the averaged weights
+            with trace_range("evaluate_ema"):
+                if native:
+                    with ema.applied():
+                        ema_correct, ema_size = evaluate(model, test_dloader, comm=comm, dst=0, native=True)
+                else:
+                    ema_correct, ema_size = evaluate(ema.module, test_dloader, comm=comm, dst=0, native=False)
         if watchdog is not None:
             watchdog.tick()
         phase("evaluate")
         check_health(comm, "before saving the checkpoint")
         if rank == 0:
             print(f"Accuracy is {correct / size:.2%}", flush=True)
+            if ema is not None:
+                print(f"EMA accuracy is {ema_correct / ema_size:.2%}", flush=True)
             with trace_range("checkpoint"):
                 state = {"model": model.state_dict()}
+                if ema is not None:
+                    state["ema"] = ema.state_dict()
                 if scaler is not None and distributed:
                     state["scaler"] = scaler.state_dict()
                 if not lr_flags_default(args):

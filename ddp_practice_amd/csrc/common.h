@@ -386,6 +386,40 @@ __device__ __forceinline__ void adam_rule4(f32x4& p, f32x4 g, f32x4& m, f32x4& v
   }
 }
 
+// torch._foreach_lerp_(self, end, w) with a scalar weight, as ATen's lerp kernel rounds it in
+// float32 (aten/src/ATen/native/Lerp.h, built with hipcc's default contraction): end - self
+// is rounded, then ONE fma in either branch --
+//   |w| <  0.5: self + w * diff         -> fma(w, diff, self)
+//   |w| >= 0.5: end - diff * (1 - w)    -> fma(-diff, 1 - w, end), 1 - w rounded (exact for w in [0.5, 1])
+// the same two lines adam_rule uses for exp_avg.  Compared with torch on the GPU in
+// profiles/ema_vs_torch.txt; tests/test_ema_gpu.py asserts the bits at w = 1e-3 and w = 0.7.
+__device__ __forceinline__ float lerp_rule(float self, float end, float w) {
+#pragma clang fp contract(off)
+  const float d = end - self;
+  return fabsf(w) < 0.5f ? __builtin_fmaf(w, d, self) : __builtin_fmaf(-d, 1.f - w, end);
+}
+__device__ __forceinline__ f32x4 lerp_rule4(f32x4 self, f32x4 end, float w) {
+  f32x4 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) r[j] = lerp_rule(self[j], end[j], w);
+  return r;
+}
+// The lerp weight of EMA update n (n = the count word, >= 1) with warm-up (optim/ema.py
+// warmup=True): decay_n = min(decay, (1 + n) / (10 + n)), weight = 1 - decay_n, in float32 and
+// in this order: nf = (float)n (exact below 2^24), a = 1 + nf, b = 10 + nf (exact below 2^24),
+// q = a / b (one rounding, correctly rounded division), then q < (float)decay ? 1 - q (one
+// rounding, exact for q >= 0.5) : w_host.  Once the constant decay wins the weight is the
+// host's float32 of the double 1 - decay, so the update is lerp_rule's without warm-up, bit for bit.
+// tests/_ema_ref.py counts these roundings.
+__device__ __forceinline__ float ema_warmup_weight(long long n, float decay, float w_host) {
+#pragma clang fp contract(off)
+  const float nf = (float)n;
+  const float a = 1.f + nf;
+  const float b = 10.f + nf;
+  const float q = a / b;
+  return q < decay ? 1.f - q : w_host;
+}
+
 // Can every workgroup of a `grid` x `threads` launch of `kernel` (dynamic LDS
 // `lds`) be resident on the current device at once?  Launches whose
 // workgroups wait on each other (grid barriers, in-kernel exchanges polled by

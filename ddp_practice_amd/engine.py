@@ -70,7 +70,7 @@ class TrainLoop:
 
     def __init__(self, model, criterion, optimizer, loader: DeviceLoader, scaler=None, use_graph: bool = True,
                  steps_per_graph: int = 16, watchdog=None, faults=None, scheduler=None,
-                 scheduler_interval: str = "step", clip_grad_norm: float | None = None):
+                 scheduler_interval: str = "step", clip_grad_norm: float | None = None, ema=None):
         self.model = model
         self.criterion = criterion
         self.optimizer = optimizer
@@ -88,6 +88,15 @@ class TrainLoop:
             # a host-side scheduler edits param_groups[i]["lr"], which a replayed graph never reads
             raise ValueError("TrainLoop: a captured step replays the learning rate it was captured with; use "
                              "optim.DeviceLR (DeviceLR.from_torch compiles a torch scheduler) or use_graph=False")
+        # ema: optim.EMA (its update() is one launch, captured with the step, whose update count
+        # lives on the device) or, on an eager loop, torch's AveragedModel.  Updated after every
+        # optimizer update, unconditionally as a torch loop that calls update_parameters after
+        # scaler.step does (a step found_inf skipped still updates the average)
+        self.ema = ema
+        if ema is not None and use_graph and loader.device.type == "cuda" and not hasattr(ema, "_snapshot"):
+            # torch's update_parameters branches on bool(n_averaged == 0) on the host
+            raise ValueError("TrainLoop: a captured step replays the host branch an averaged model took at "
+                             "capture (copy or average, forever); use optim.EMA or use_graph=False")
         self.device = loader.device
         self.use_graph = use_graph and self.device.type == "cuda"
         self.spg = max(1, steps_per_graph)
@@ -189,9 +198,28 @@ class TrainLoop:
                         flush()
                     self._clip()
                 self.optimizer.step()
+        if self.ema is not None:
+            self._ema_update()
         if self.scheduler is not None and self.scheduler_interval == "step":
             self.scheduler.step()
         return loss
+
+    def _ema_update(self):
+        if hasattr(self.ema, "update_parameters"):  # torch.optim.swa_utils.AveragedModel (eager loops)
+            m = self.model
+            wrapped = type(m).__name__ == "DistributedDataParallel" and hasattr(m, "module")
+            self.ema.update_parameters(m.module if wrapped else m)
+        else:
+            self.ema.update()
+
+    def _snapshot_all(self):
+        return (_snapshot(self.model, self.optimizer, self.scaler, self.scheduler),
+                self.ema._snapshot() if self.ema is not None else None)
+
+    def _restore_all(self, snap):
+        _restore(self.model, self.optimizer, self.scaler, snap[0], self.scheduler)
+        if snap[1] is not None:
+            self.ema._restore(snap[1])
 
     def _eager_step(self, images=None, labels=None, fill=True):
         """One un-captured step (CPU, tail batches, steps with an injected fault)."""
@@ -215,14 +243,13 @@ class TrainLoop:
             return None
         if k in self._graphs:
             return self._graphs[k]
-        snap = _snapshot(self.model, self.optimizer, self.scaler, self.scheduler)
+        snap = self._snapshot_all()
         g = CapturedStep(lambda: self._step(), warmup=2, steps_per_graph=k,
-                         pre_capture=lambda: _restore(self.model, self.optimizer, self.scaler, snap,
-                                                      self.scheduler))
+                         pre_capture=lambda: self._restore_all(snap))
         ctr = self.loader._ctr.clone() if self.loader._ctr is not None else None
         ok = g.capture()
         # undo the warm-up step's data consumption and parameter update
-        _restore(self.model, self.optimizer, self.scaler, snap, self.scheduler)
+        self._restore_all(snap)
         if ctr is not None:
             self.loader._ctr.copy_(ctr)
         if not ok:
