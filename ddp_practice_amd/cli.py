@@ -45,6 +45,13 @@ Additive flags (all optional; defaults reproduce the reference):
                                       --ema-warmup (native only) uses min(D, (1 + n) / (10 + n)) at update n.
                                       ``EMA accuracy is xx.xx%`` follows the accuracy line, the checkpoint
                                       gains "ema" (AveragedModel's layout), --metrics-file rows ema_updates
+  --accum-steps K                     one optimizer update per window of K micro-batches (default 1; -b stays
+                                      the micro-batch per rank: the effective batch is K * b * world).  One
+                                      native launch per micro-step folds the fresh gradients into float32
+                                      accumulators (optim/accum.py), DDP averages once per window; --impl
+                                      torch: the textbook idiom (loss / K, no_sync()).  A window never spans
+                                      an epoch; schedules, --warmup-steps and the resume position count
+                                      updates, ceil(batches / K) per epoch; --metrics-file rows carry updates
   --resume PATH [--start-epoch N]     load {"model"[, "scaler"][, "optimizer", "lr_scheduler"][, "ema"]} before
                                       training (the last three are written only with a non-default flag above)
   --watchdog-timeout S                abort + exit when no progress for S seconds (default at
@@ -100,6 +107,8 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
     parser.add_argument("--ema-buffers", action="store_true", help="average the float buffers too (else: copied)")
     parser.add_argument("--ema-warmup", action="store_true",
                         help="update n uses min(decay, (1 + n) / (10 + n)); native route only")
+    parser.add_argument("--accum-steps", type=int, default=1,
+                        help="micro-batches per optimizer update (gradient accumulation; default 1)")
     parser.add_argument("--image-size", type=int, default=224, help="resnet50: synthetic image side")
     parser.add_argument("--num-classes", type=int, default=1000, help="resnet50: synthetic label count")
     if distributed:
@@ -184,6 +193,14 @@ def clip_flag(args) -> float | None:
     if v < 0.0 or v != v:
         raise SystemExit(f"error: --clip-grad-norm expects a norm >= 0 (0 = off), not {v}")
     return v if v > 0.0 else None
+
+
+def accum_flag(args) -> int:
+    """--accum-steps as TrainLoop's ``accum_steps``; exits on a value below 1."""
+    k = int(getattr(args, "accum_steps", 1))
+    if k < 1:
+        raise SystemExit(f"error: --accum-steps expects a number of micro-batches >= 1, not {k}")
+    return k
 
 
 def ema_flags(args) -> dict | None:
@@ -302,13 +319,16 @@ class _Metrics:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
-    def epoch(self, epoch: int, images: int, steps: int, scaler=None, lr=None, grad_norm=None, ema_updates=None):
+    def epoch(self, epoch: int, images: int, steps: int, scaler=None, lr=None, grad_norm=None, ema_updates=None,
+              updates=None):
         if self.path is None:
             return
         self._sync()
         dt = time.perf_counter() - self.t0
         rec = {"epoch": epoch, "steps_per_rank": steps, "images": images, "seconds": round(dt, 4),
                "images_per_s": round(images / dt, 1) if dt > 0 else None, "world_size": self.world}
+        if updates is not None:
+            rec["updates"] = int(updates)  # optimizer updates so far (steps_per_rank / --accum-steps per epoch)
         if scaler is not None and scaler.is_enabled():
             rec["loss_scale"] = scaler.get_scale()
         if lr is not None:
@@ -339,6 +359,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     phase("run")
     clip = clip_flag(args)
     ema_kw = ema_flags(args)
+    accum = accum_flag(args)
     import torch
 
     import ddp_practice_amd.distributed as dist
@@ -462,7 +483,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     # The schedule, built once as a torch scheduler: --impl torch steps it; the native path
     # compiles it into a device table (optim.DeviceLR.from_torch), whose step() is captured
     # into the step graph.  Position on resume: the file's, else the start of --start-epoch.
-    spe = len(train_dloader)
+    spe = -(-len(train_dloader) // accum)  # optimizer updates per epoch: the last window may be short
     make_sched, interval = scheduler_factory(args, (args.start_epoch + args.epochs) * spe)
     scheduler = None
     if make_sched is not None:
@@ -501,7 +522,8 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     # ResNet-50: hundreds of launches per step, one step per captured graph is enough
     loop = TrainLoop(model, criterion, optimizer, train_dloader, scaler, use_graph=native and not args.no_graph,
                      steps_per_graph=1 if resnet else 16, watchdog=watchdog, faults=faults, scheduler=scheduler,
-                     scheduler_interval=interval or "step", clip_grad_norm=clip, ema=ema)
+                     scheduler_interval=interval or "step", clip_grad_norm=clip, ema=ema, accum_steps=accum,
+                     accum_impl="native" if native else "torch")
     metrics = _Metrics(args.metrics_file, rank, world, dev)
     metrics.start()
     try:
@@ -516,7 +538,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
                           lr=(lambda: scheduler.get_last_lr()[0]) if scheduler is not None
                           else optimizer.param_groups[0]["lr"],
                           grad_norm=loop.grad_norm if clip is not None else None,
-                          ema_updates=ema.n_averaged if ema is not None else None)
+                          ema_updates=ema.n_averaged if ema is not None else None, updates=loop.global_step)
             phase(f"epoch {epoch}")
         if loop.graph_error is not None and rank == 0:
             print(f"[ddp_practice_amd] hipGraph capture failed, ran eagerly: {loop.graph_error!r}", file=sys.stderr)

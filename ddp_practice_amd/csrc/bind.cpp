@@ -25,6 +25,7 @@ void register_conv_igemm(pybind11::module& m);
 void register_adam(pybind11::module& m);
 void register_clip(pybind11::module& m);
 void register_ema(pybind11::module& m);
+void register_accum(pybind11::module& m);
 }
 
 // sha1 of the sources this library was built from (build.py generates it; _ext.py compares
@@ -67,4 +68,5 @@ PYBIND11_MODULE(_C, m) {
   dpa::register_adam(m);
   dpa::register_clip(m);
   dpa::register_ema(m);
+  dpa::register_accum(m);
 }

@@ -70,7 +70,8 @@ class TrainLoop:
 
     def __init__(self, model, criterion, optimizer, loader: DeviceLoader, scaler=None, use_graph: bool = True,
                  steps_per_graph: int = 16, watchdog=None, faults=None, scheduler=None,
-                 scheduler_interval: str = "step", clip_grad_norm: float | None = None, ema=None):
+                 scheduler_interval: str = "step", clip_grad_norm: float | None = None, ema=None,
+                 accum_steps: int = 1, accum_impl: str = "native"):
         self.model = model
         self.criterion = criterion
         self.optimizer = optimizer
@@ -135,6 +136,22 @@ class TrainLoop:
             else:
                 self._clip_mode = "native" if isinstance(optimizer, SGD) else "torch"
                 self._norm_words = torch.tensor([0.0, 1.0], dtype=torch.float32, device=self.device)
+        # accum_steps K > 1: an optimizer update per window of K micro-batches (optim/accum.py).
+        # Created after the deferral above: the accumulator asks who owns the DDP average.
+        # global_step, the fault steps, the watchdog note, the EMA count, Adam's step word and
+        # the DeviceLR position all count optimizer updates, not micro-batches
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+            raise ValueError(f"accum_steps must be an int >= 1, not {accum_steps!r}")
+        if accum_impl not in ("native", "torch"):
+            raise ValueError(f"accum_impl must be 'native' or 'torch', not {accum_impl!r}")
+        self.accum_steps = accum_steps
+        # accum_impl "torch": the textbook idiom instead (loss / K, autograd's accumulation into
+        # .grad, no_sync() on the non-final micro-steps), the --impl torch runs' reference
+        self.accum = None
+        if accum_steps > 1 and accum_impl == "native":
+            from .optim import GradAccumulator
+
+            self.accum = GradAccumulator(optimizer, accum_steps, model if hasattr(model, "no_sync") else None)
         self.global_step = 0
         # the model's first kernel gathers the batch itself (no gather launch per step)
         from .data.loader import accepts_deferred
@@ -175,6 +192,16 @@ class TrainLoop:
         if self.scaler is not None:
             with trace_range("backward"):
                 self.scaler.scale(loss).backward()
+        else:
+            with trace_range("backward"):
+                loss.backward()
+        self._update(before_update)
+        return loss
+
+    def _update(self, before_update=None):
+        """The optimizer update over complete gradients: unscale / clip / step / scale update,
+        then the weight average and the per-step schedule."""
+        if self.scaler is not None:
             if before_update is not None:
                 flush = getattr(self.optimizer, "_flush_deferred", None)
                 if flush is not None:
@@ -187,8 +214,6 @@ class TrainLoop:
                 self.scaler.step(self.optimizer)
                 self.scaler.update()
         else:
-            with trace_range("backward"):
-                loss.backward()
             if before_update is not None:
                 before_update()
             with trace_range("optimizer"):
@@ -202,6 +227,45 @@ class TrainLoop:
             self._ema_update()
         if self.scheduler is not None and self.scheduler_interval == "step":
             self.scheduler.step()
+
+    # -- one window of micro-steps and its update (accum_steps > 1; what gets captured)
+    def _window(self, items=None, before_update=None):
+        """``items``: one entry per micro-step, None (the next full batch, filled into the static
+        buffers) or an (images, labels) pair already filled; default: ``accum_steps`` full
+        batches.  The last entry closes the window, however short it is."""
+        items = [None] * self.accum_steps if items is None else items
+        idiom = self.accum is None
+        if idiom:
+            self.optimizer.zero_grad(set_to_none=True)
+        loss = None
+        for i, it in enumerate(items):
+            last = i == len(items) - 1
+            if it is None:
+                self.loader.fill_(self.images, self.labels, defer=self._defer)
+                images, labels = self.images, self.labels
+            else:
+                images, labels = it
+            if not idiom:
+                ctx = self.accum.micro_step()
+            elif not last and hasattr(self.model, "no_sync"):
+                ctx = self.model.no_sync()
+            else:
+                ctx = contextlib.nullcontext()
+            with ctx:
+                with trace_range("forward"):
+                    outputs = self.model(images)
+                    loss = self.criterion(outputs, labels)
+                if idiom:
+                    loss = loss / self.accum_steps
+                else:
+                    self.optimizer.zero_grad(set_to_none=True)
+                with trace_range("backward"):
+                    (self.scaler.scale(loss) if self.scaler is not None else loss).backward()
+            if not idiom:
+                with trace_range("accumulate"):
+                    done = self.accum.accumulate(last=last)
+                assert done == last
+        self._update(before_update)
         return loss
 
     def _ema_update(self):
@@ -221,15 +285,19 @@ class TrainLoop:
         if snap[1] is not None:
             self.ema._restore(snap[1])
 
-    def _eager_step(self, images=None, labels=None, fill=True):
-        """One un-captured step (CPU, tail batches, steps with an injected fault)."""
+    def _eager_step(self, images=None, labels=None, fill=True, items=None):
+        """One un-captured update (CPU, tail batches, steps with an injected fault): a step, or with
+        accum_steps > 1 a window (``items``: see ``_window``)."""
         step = self.global_step
         hook = None
         if self.faults is not None:
             self.faults.before_step(step)
             params = [p for g in self.optimizer.param_groups for p in g["params"]]
             hook = lambda: self.faults.corrupt_grads(step, params)  # noqa: E731
-        self._step(images, labels, fill=fill, before_update=hook)
+        if self.accum_steps > 1:
+            self._window(items, before_update=hook)
+        else:
+            self._step(images, labels, fill=fill, before_update=hook)
         self.global_step += 1
         self._tick()
 
@@ -244,7 +312,9 @@ class TrainLoop:
         if k in self._graphs:
             return self._graphs[k]
         snap = self._snapshot_all()
-        g = CapturedStep(lambda: self._step(), warmup=2, steps_per_graph=k,
+        # accum_steps > 1: a graph holds k whole windows
+        g = CapturedStep((lambda: self._window()) if self.accum_steps > 1 else (lambda: self._step()),
+                         warmup=2, steps_per_graph=k,
                          pre_capture=lambda: self._restore_all(snap))
         ctr = self.loader._ctr.clone() if self.loader._ctr is not None else None
         ok = g.capture()
@@ -259,8 +329,61 @@ class TrainLoop:
         self._graphs[k] = g
         return g
 
+    def _run_epoch_windows(self) -> None:
+        """run_epoch with accum_steps K > 1: ``nfull // K`` whole windows, graph-replayed in
+        graphs of ``max(1, steps_per_graph // K)`` windows (about today's micro-steps per
+        graph) and then of one; the epoch's last window is short when the batches are no
+        multiple of K -- the leftover full batches plus the sampler's partial tail batch --
+        and runs eagerly.  A window never spans an epoch."""
+        K = self.accum_steps
+        sizes = self.loader.batch_sizes()
+        B = self.loader.batch_size
+        nfull = sum(1 for b in sizes if b == B)
+        tail = [b for b in sizes if b != B]
+        self.loader.start_epoch()
+        if self.accum is not None:
+            self.accum.reset()
+        nwin, left = divmod(nfull, K)
+        wpg = max(1, self.spg // K)
+        done = 0
+        faults = self.faults
+        with trace_range("train_epoch"):
+            if self.use_graph and nwin > 0:
+                big = self._graph(wpg) if (wpg > 1 and nwin >= wpg) else None
+                while big is not None and nwin - done >= wpg:
+                    if faults is not None and faults.pending_in(self.global_step, self.global_step + wpg):
+                        break  # run the chunk holding the faulty update window by window
+                    big.run()
+                    done += wpg
+                    self.global_step += wpg
+                    self._tick()
+                if nwin - done > 0:
+                    one = self._graph(1)
+                    while one is not None and done < nwin:
+                        if faults is not None and faults.pending_in(self.global_step, self.global_step + 1):
+                            self._eager_step()
+                        else:
+                            one.run()
+                            self.global_step += 1
+                            self._tick()
+                        done += 1
+            while done < nwin:  # eager fallback (CPU, or capture failed)
+                self._eager_step()
+                done += 1
+            items = [None] * left
+            for i, b in enumerate(tail):
+                imgs, labels = self.loader.static_batch(b)
+                self.loader._fill_tail(imgs, labels, nfull + i)
+                items.append((imgs, labels))
+            for s in range(0, len(items), K):
+                self._eager_step(items=items[s:s + K])
+        if self.scheduler is not None and self.scheduler_interval == "epoch":
+            self.scheduler.step()
+
     def run_epoch(self) -> None:
         self.model.train()
+        if self.accum_steps > 1:
+            return self._run_epoch_windows()
         sizes = self.loader.batch_sizes()
         B = self.loader.batch_size
         nfull = sum(1 for b in sizes if b == B)

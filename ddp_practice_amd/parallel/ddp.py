@@ -284,6 +284,51 @@ class DistributedDataParallel(nn.Module):
         self.reducer.set_require_inplace(True)
         return True
 
+    # -------------------------------------- gradient accumulation (optim/accum.py)
+    def defer_grad_sync_for(self, optimizer) -> bool:
+        """Opt-in for ``optim.GradAccumulator``: one gradient average per window of micro-steps.
+
+        The reducer is put in defer mode (any communicator): every backward leaves the
+        buckets holding this rank's gradients.  The accumulator drops the pending average of
+        a non-final micro-step (``drop_deferred_grad_sync``) and, after writing the window's
+        mean into the bucket views, leaves the final one to the optimizer that owns the
+        deferral (``defer_grad_sync_to`` succeeded) or runs it (``run_deferred_grad_sync``).
+        Needs ``gradient_as_bucket_view=True`` (the average lands where ``.grad`` lives), no
+        ``find_unused_parameters`` and an optimizer that holds exactly this module's
+        parameters.  Returns whether it was enabled; otherwise the caller runs its
+        micro-steps under ``no_sync()`` and averages itself."""
+        if self.reducer is None or not self.gradient_as_bucket_view or self.find_unused_parameters:
+            return False
+        opt_params = [p for g in optimizer.param_groups for p in g["params"]]
+        if {id(p) for p in opt_params} != {id(p) for p in self._params}:
+            return False
+        self.reducer.set_defer(True)
+        return True
+
+    @property
+    def averages_gradients(self) -> bool:
+        """Whether a backward through this module averages gradients over ranks at all (a
+        reducer exists: more than one rank, or collectives forced)."""
+        return self.reducer is not None
+
+    def grad_sync_deferred_to(self, optimizer) -> bool:
+        """Whether ``optimizer`` owns this reducer's deferred average (``defer_grad_sync_to``)."""
+        d = getattr(optimizer, "_deferred_ddp", None)
+        return d is not None and d[0] is self.reducer
+
+    def drop_deferred_grad_sync(self) -> None:
+        """Forget the pending average of the last backward: its gradients stay rank-local."""
+        if self.reducer is not None:
+            self.reducer.consume_deferred()
+
+    def run_deferred_grad_sync(self) -> None:
+        """Run the pending bucket all-reduces now, over whatever ``.grad`` holds."""
+        if self.reducer is not None:
+            self.reducer.flush_deferred()
+
+    def deferred_grad_sync_pending(self) -> bool:
+        return self.reducer is not None and bool(self.reducer.deferred_pending())
+
     # -------------------------------------------------------------- utilities
     def bucket_sizes_bytes(self) -> list[int]:
         if self.reducer is None:
