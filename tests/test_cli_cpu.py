@@ -120,7 +120,10 @@ def test_shared_cu_mask_gives_each_rank_its_own_cus(monkeypatch):
     from ddp_practice_amd.runtime.device import shared_cu_mask
 
     for k in ("HSA_CU_MASK", "DPA_RESIDENT_CUS", "DPA_SHARED_CUS", "DPA_SHARED_CU_MASK"):
-        monkeypatch.delenv(k, raising=False)
+        # set first: deleting an absent key registers nothing to undo, and the values shared_cu_mask
+        # writes below would stay in the session (every rank spawned by a later test on 32 CUs)
+        monkeypatch.setenv(k, "")
+        monkeypatch.delenv(k)
     assert shared_cu_mask(2, 1) is None and "HSA_CU_MASK" not in os.environ
     masks = [shared_cu_mask(8, r) for r in range(8)]
     assert masks[0] == "0:0-31" and masks[7] == "0:224-255" and os.environ["DPA_RESIDENT_CUS"] == "32"
