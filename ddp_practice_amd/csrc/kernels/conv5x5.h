@@ -60,11 +60,21 @@ constexpr int W2F_LEN = W2F_ROWS * W2F_PITCH, W2D_LEN = W2D_ROWS * W2D_PITCH;
 // the pack workgroups of a launch and the elements per lane: fixed, whatever the batch
 constexpr int W2P_WGS = 26, W2P_IT = 4;
 static_assert(W2P_WGS * W2P_IT * NTHR >= W2F_LEN + W2D_LEN, "the pack workgroups cover both packs");
+// The fc weights of the one-launch head (convnet_head.hip head_row_kernel PK), packed by the
+// same launch in fcp_nm(N) further workgroups behind the W2P_WGS: [FCP_LANES][NM][8] of T,
+// entry [lane][n][i] = T(wfc[n][lane + 256 i]), zero where n >= N, lane + 256 i >= FCP_K or
+// i = 7 -- a head lane's class row is one 16-B granule, already in the compute dtype, instead
+// of 7 scalar f32 loads and 7 roundings that every one of the head's workgroups repeated.
+// NM: the class count the head's register tiles are sized for (what head_step selects).
+// (the layout constants: convblock_bn.h FCP_*, shared with the head)
 template <typename T>
 struct WPack {
   const float* w2 = nullptr;  // [32][16][5][5] f32 master weights
   T* fwd = nullptr;           // [W2F_LEN]
   T* dgrad = nullptr;         // [W2D_LEN]
+  const float* wfc = nullptr; // [N][FCP_K] f32 master fc weights (with fcp)
+  T* fcp = nullptr;           // [fcp_len(NM)] or null: no fc pack workgroups in the launch
+  int N = 0, NM = 0;          // classes; fcp_nm(N) = the launch's fc pack workgroups
 };
 // Pack workgroup wg of W2P_WGS: element (wg * W2P_IT + i) * NTHR + lane of
 // [fwd | dgrad].  Compile-time trip counts and no blockDim / gridDim (hidden-argument loads
@@ -104,6 +114,35 @@ __device__ __forceinline__ void pack_w2(const WPack<T>& pk, const int wg) {
       pk.dgrad[e - W2F_LEN] = o;
   }
   DPA_STAMP(7);
+}
+
+// fc pack workgroup n of pk.NM: class n for every head lane.  The same discipline as pack_w2:
+// compile-time trip counts, no blockDim / gridDim, the 7 loads of the class row (coalesced
+// across the lanes; clamped and unconditional) issued before the first conversion, one 16-B
+// store per lane.  The padding (n >= N, features >= FCP_K, element 7) is written every step.
+template <typename T>
+__device__ __forceinline__ void pack_fc(const WPack<T>& pk, const int n) {
+  static_assert(FCP_LANES == NTHR, "one lane of a pack workgroup per head lane");
+  if constexpr (sizeof(T) == 2) {
+    const int tid = threadIdx.x;
+    DPA_STAMP(0);
+    const float* row = pk.wfc + (size_t)min(n, pk.N - 1) * FCP_K;
+    float v[FCP_IT];
+#pragma unroll
+    for (int i = 0; i < FCP_IT; ++i) v[i] = row[min(tid + FCP_LANES * i, FCP_K - 1)];
+    u16x8 o;
+#pragma unroll
+    for (int i = 0; i < FCP_IT; ++i) {
+      const bool pad = n >= pk.N || tid + FCP_LANES * i >= FCP_K;
+      const T t = Cvt<T>::from_f(pad ? 0.f : v[i]);
+      unsigned short bits;
+      __builtin_memcpy(&bits, &t, 2);
+      o[i] = bits;
+    }
+    o[7] = 0;
+    *reinterpret_cast<u16x8*>(pk.fcp + ((size_t)tid * pk.NM + n) * 8) = o;
+    DPA_STAMP(7);
+  }
 }
 
 // Batch gather fused into the first conv (PRO 3): the input image is read from
@@ -784,7 +823,11 @@ conv5x5_kernel(const T* __restrict__ x, const float* __restrict__ w, const float
   if constexpr (WPK == 2) {  // the workgroups behind the conv role's pack the layer-2 weights
     const int nconv = gin.nimg * nsplit;
     if ((int)blockIdx.x >= nconv) {
-      pack_w2<T>(pk, (int)blockIdx.x - nconv);
+      const int pw = (int)blockIdx.x - nconv;
+      if (pw < W2P_WGS)
+        pack_w2<T>(pk, pw);
+      else  // the head's fc weights (launched only with pk.fcp: pk.NM workgroups)
+        pack_fc<T>(pk, pw - W2P_WGS);
       return;
     }
   }

@@ -42,6 +42,14 @@ namespace cb {
 
 constexpr int NTHR = 256;
 
+// The head's packed fc weights (conv5x5.h pack_fc writes them, convnet_head.hip head_row_kernel
+// PK reads them): [FCP_LANES][NM][8] elements, NM = fcp_nm(N) the class count the head's
+// register tiles are sized for.
+constexpr int FCP_K = 32 * 49, FCP_LANES = 256, FCP_IT = (FCP_K + FCP_LANES - 1) / FCP_LANES;
+static_assert(FCP_IT == 7, "a head lane's features of one class fit one 16-B granule of 8");
+__host__ __device__ constexpr int fcp_nm(int N) { return N > 10 ? 16 : 10; }
+__host__ __device__ constexpr int fcp_len(int NM) { return FCP_LANES * NM * 8; }
+
 // Final statistics buffer written by bn_relu_pool (read by the backward):
 // [0,C) sum(y-shift) | [C,2C) sum((y-shift)^2) | [2C] count | [2C+1,3C+1) shift
 __host__ __device__ constexpr int stats_len(int C) { return 3 * C + 1; }

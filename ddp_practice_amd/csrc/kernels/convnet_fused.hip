@@ -393,11 +393,35 @@ static void check_conv1_pack(const at::Tensor& x, const at::Tensor& w1, const at
               wpk_f.scalar_type() == x.scalar_type() && wpk_d.scalar_type() == x.scalar_type());
 }
 
+// The head's fc pack (cb::pack_fc) hosted by a conv1 launch: fills pk and returns the launch's
+// extra workgroups, cb::fcp_nm(N); 0 without a buffer (the grid and the kernel's path are then
+// what they were).  bf16 / fp16 only: the fp32 head reads the master weights as they are.
+template <typename T>
+static int fc_pack_args(cb::WPack<T>& pk, const c10::optional<at::Tensor>& wfc, const c10::optional<at::Tensor>& wfc_pk,
+                        at::ScalarType st) {
+  if (!wfc_pk.has_value()) return 0;
+  TORCH_CHECK(wfc.has_value(), "fc pack: wfc and wfc_pk go together");
+  DPA_CHECK_INPUT(*wfc); DPA_CHECK_INPUT(*wfc_pk);
+  TORCH_CHECK(st != at::kFloat, "fc pack: bf16 / fp16 only");
+  TORCH_CHECK(wfc->scalar_type() == at::kFloat && wfc->dim() == 2 && wfc->size(1) == cb::FCP_K && wfc->size(0) >= 1 &&
+              wfc->size(0) <= 16, "fc pack: fp32 fc.weight [N <= 16][1568]");
+  const int N = (int)wfc->size(0), NM = cb::fcp_nm(N);
+  TORCH_CHECK(wfc_pk->scalar_type() == st && wfc_pk->numel() == cb::fcp_len(NM), "fc pack: wfc_pk holds [256][", NM,
+              "][8] elements of the compute dtype");
+  pk.wfc = wfc->data_ptr<float>();
+  pk.fcp = dptr<T>(*wfc_pk);
+  pk.N = N;
+  pk.NM = NM;
+  return NM;
+}
+
 // Layer-1 conv (+BN1 sums when training) whose launch also packs the layer-2 weights: B * SPLIT conv
-// workgroups, then cb::W2P_WGS pack workgroups (cb::pack_w2), which write no fslab1 row.
+// workgroups, then cb::W2P_WGS pack workgroups (cb::pack_w2), which write no fslab1 row; with
+// wfc_pk, cb::fcp_nm(N) more that pack the head's fc weights (cb::pack_fc).
 void conv1_fwd_pack(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor y1, c10::optional<at::Tensor> fslab1,
                     c10::optional<at::Tensor> fstats1, c10::optional<at::Tensor> shift1, at::Tensor w2,
-                    at::Tensor wpk_f, at::Tensor wpk_d) {
+                    at::Tensor wpk_f, at::Tensor wpk_d, c10::optional<at::Tensor> wfc,
+                    c10::optional<at::Tensor> wfc_pk) {
   DPA_CHECK_INPUT(x); DPA_CHECK_INPUT(w1); DPA_CHECK_INPUT(b1); DPA_CHECK_INPUT(y1); DPA_CHECK_INPUT(w2);
   DPA_CHECK_INPUT(wpk_f); DPA_CHECK_INPUT(wpk_d);
   const int B = (int)x.size(0);
@@ -411,15 +435,16 @@ void conv1_fwd_pack(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor y1, c
   with_t(dt_of(x), [&](auto tag) {
     typedef decltype(tag) T;
     cb::WPack<T> pk{w2.data_ptr<float>(), dptr<T>(wpk_f), dptr<T>(wpk_d)};
+    const int nfcp = fc_pack_args<T>(pk, wfc, wfc_pk, x.scalar_type());
     cb::GatherIn gin;  // no gather: just the conv workgroup count (the pack role starts behind it)
     gin.nimg = B;
     if (st)
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 0, 0, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS),
+      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 0, 0, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS + nfcp),
                          dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(),
                          dptr<T>(y1), fslab1->data_ptr<float>(), fstats1->data_ptr<float>(),
                          shift1->data_ptr<float>(), S::SPLIT, PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{}, nullptr, pk, gin);
     else
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 1, 0, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS),
+      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 1, 0, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS + nfcp),
                          dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(),
                          dptr<T>(y1), nullptr, nullptr, nullptr, S::SPLIT, PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{},
                          nullptr, pk, gin);
@@ -433,7 +458,8 @@ void conv1_fwd_pack(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor y1, c
 void conv1_fwd_pack_gather(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor y1, at::Tensor fslab1,
                            at::Tensor fstats1, at::Tensor shift1, at::Tensor w2, at::Tensor wpk_f, at::Tensor wpk_d,
                            at::Tensor imgs, at::Tensor labels, at::Tensor order, at::Tensor ctr, at::Tensor lab_out,
-                           double scale, double shift) {
+                           double scale, double shift, c10::optional<at::Tensor> wfc,
+                           c10::optional<at::Tensor> wfc_pk) {
   DPA_CHECK_INPUT(x); DPA_CHECK_INPUT(w1); DPA_CHECK_INPUT(b1); DPA_CHECK_INPUT(y1); DPA_CHECK_INPUT(w2);
   DPA_CHECK_INPUT(wpk_f); DPA_CHECK_INPUT(wpk_d); DPA_CHECK_INPUT(imgs); DPA_CHECK_INPUT(labels);
   DPA_CHECK_INPUT(order); DPA_CHECK_INPUT(ctr); DPA_CHECK_INPUT(lab_out);
@@ -461,7 +487,8 @@ void conv1_fwd_pack_gather(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tenso
   with_t(dt_of(x), [&](auto tag) {
     typedef decltype(tag) T;
     cb::WPack<T> pk{w2.data_ptr<float>(), dptr<T>(wpk_f), dptr<T>(wpk_d)};
-    hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 0, 3, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS),
+    const int nfcp = fc_pack_args<T>(pk, wfc, wfc_pk, x.scalar_type());
+    hipLaunchKernelGGL((cb::conv5x5_kernel<T, 1, 16, 28, 28, 0, 3, 0, 2>), dim3(B * S::SPLIT + cb::W2P_WGS + nfcp),
                        dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x), w1.data_ptr<float>(), b1.data_ptr<float>(),
                        dptr<T>(y1), fslab1.data_ptr<float>(), fstats1.data_ptr<float>(), shift1.data_ptr<float>(),
                        S::SPLIT, PoolIn<T>{}, BwdIn<T>{}, BwdEpi<T>{}, nullptr, pk, gin);
@@ -976,8 +1003,15 @@ void register_convnet_fused(pybind11::module& m) {
   s.def("head_bwd", &cnf::head_bwd);
   s.def("head_bwd_lds", &cnf::head_bwd_lds);
   s.def("dgrad2_rows", &cnf::dgrad2_rows, py::arg("B"), py::arg("fp32") = false);
-  s.def("conv1_fwd_pack", &cnf::conv1_fwd_pack);
-  s.def("conv1_fwd_pack_gather", &cnf::conv1_fwd_pack_gather);
+  // wfc, wfc_pk (trailing, optional): the launch also packs the head's fc weights (cb::pack_fc)
+  s.def("conv1_fwd_pack", &cnf::conv1_fwd_pack, py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("y1"),
+        py::arg("fslab1"), py::arg("fstats1"), py::arg("shift1"), py::arg("w2"), py::arg("wpk_f"), py::arg("wpk_d"),
+        py::arg("wfc") = py::none(), py::arg("wfc_pk") = py::none());
+  s.def("conv1_fwd_pack_gather", &cnf::conv1_fwd_pack_gather, py::arg("x"), py::arg("w1"), py::arg("b1"),
+        py::arg("y1"), py::arg("fslab1"), py::arg("fstats1"), py::arg("shift1"), py::arg("w2"), py::arg("wpk_f"),
+        py::arg("wpk_d"), py::arg("imgs"), py::arg("labels"), py::arg("order"), py::arg("ctr"), py::arg("lab_out"),
+        py::arg("scale"), py::arg("shift"), py::arg("wfc") = py::none(), py::arg("wfc_pk") = py::none());
+  s.attr("FCP_LANES") = cb::FCP_LANES;
 #ifdef DPA_TIMING
   s.def("read_stamps", []() {
     auto out = at::empty({DPA_MAX_STAMP_BLOCKS, DPA_NSTAMPS}, at::TensorOptions().dtype(at::kLong));

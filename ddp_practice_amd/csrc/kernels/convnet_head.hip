@@ -80,12 +80,27 @@ struct HeadRow {
 // lds_barrier (common.h): the global stores (pooled outputs, dp2) and the loss atomic are not waited
 
 
+// a 16-bit element of the packed fc weights as the float the GEMV multiplies
+template <typename T>
+__device__ __forceinline__ float unpack16(unsigned short bits) {
+  if constexpr (std::is_same<T, __hip_bfloat16>::value) {
+    return __builtin_bit_cast(float, (unsigned)bits << 16);  // bf16: the float's high half
+  } else {
+    return (float)__builtin_bit_cast(_Float16, bits);
+  }
+}
+
 // NM: classes the register tiles are sized for (>= N); NT: workgroup size (256 | 1024)
-template <typename T, int NM, int NT>
+// PK (NT 256, bf16 / fp16): the fc weights come from wfc_pk, packed by the step's conv1 launch
+// (cb::pack_fc: [256 lanes][NM][8] of T, already rounded, padding zero): NM 16-B loads per lane
+// instead of NM * 7 scalar f32 loads, and no rounding pass.  Same values, same accumulation
+// order: every output is bitwise what the unpacked kernel gives.
+template <typename T, int NM, int NT, bool PK = false>
 __global__ void __launch_bounds__(NT)
 head_row_kernel(const T* __restrict__ y, BNParams bn, const float* __restrict__ wfc, const float* __restrict__ bfc,
                 T* __restrict__ logits, T* __restrict__ p_out, uint8_t* __restrict__ idx_out,
-                T* __restrict__ xh_out, int B, int N, HeadRow hr) {
+                T* __restrict__ xh_out, int B, int N, HeadRow hr, const T* __restrict__ wfc_pk) {
+  static_assert(!PK || (NT == cb::FCP_LANES && sizeof(T) == 2 && NM == cb::fcp_nm(NM)), "packed fc weights: 256 lanes, 16-bit");
   typedef typename Pair2<T>::type P;
   constexpr int IT = (K + NT - 1) / NT;  // pooled features per lane (7 | 2)
   constexpr int NW = NT / 64;
@@ -114,11 +129,18 @@ head_row_kernel(const T* __restrict__ y, BNParams bn, const float* __restrict__ 
     bot[i] = src[W / 2];
   }
   float wq[NM][IT];  // fc weights of this lane's features, every class
+  u16x8 wraw[PK ? NM : 1];  // PK: the packed granules (this lane's class rows)
+  if constexpr (PK) {
+    const u16x8* src = reinterpret_cast<const u16x8*>(wfc_pk) + (size_t)tid * NM;
 #pragma unroll
-  for (int n = 0; n < NM; ++n) {
-    const float* wr = wfc + (size_t)min(n, N - 1) * K;
+    for (int n = 0; n < NM; ++n) wraw[n] = src[n];
+  } else {
 #pragma unroll
-    for (int i = 0; i < IT; ++i) wq[n][i] = wr[min(tid + i * NT, K - 1)];
+    for (int n = 0; n < NM; ++n) {
+      const float* wr = wfc + (size_t)min(n, N - 1) * K;
+#pragma unroll
+      for (int i = 0; i < IT; ++i) wq[n][i] = wr[min(tid + i * NT, K - 1)];
+    }
   }
   float bias[NM];
 #pragma unroll
@@ -159,11 +181,18 @@ head_row_kernel(const T* __restrict__ y, BNParams bn, const float* __restrict__ 
       xh_out[o] = xq;
     }
   }
-  // fc weights in the compute dtype (autocast casts the fp32 master weight)
+  // fc weights in the compute dtype (autocast casts the fp32 master weight; PK: cast by the
+  // pack, classes >= N zero there)
 #pragma unroll
   for (int n = 0; n < NM; ++n)
 #pragma unroll
-    for (int i = 0; i < IT; ++i) wq[n][i] = n < N ? rnd_t<T>(wq[n][i]) : 0.f;
+    for (int i = 0; i < IT; ++i) {
+      if constexpr (PK) {
+        wq[n][i] = unpack16<T>(wraw[n][i]);
+      } else {
+        wq[n][i] = n < N ? rnd_t<T>(wq[n][i]) : 0.f;
+      }
+    }
   // 3. logits = p . W^T + bias: lane-partial dot products, reduced over the wave
   //    (butterfly) and over the 4 waves (LDS, fixed order)
 #pragma unroll
@@ -332,7 +361,7 @@ void head_step(at::Tensor y2, at::Tensor fslab2, at::Tensor fstats2, at::Tensor 
                int64_t ignore_index, double smoothing, c10::optional<at::Tensor> scale, at::Tensor state,
                at::Tensor loss, at::Tensor dlog, c10::optional<at::Tensor> dls, c10::optional<at::Tensor> dp2,
                c10::optional<at::Tensor> bsum_rows, std::shared_ptr<xgmi::XgmiComm> xc,
-               c10::optional<at::Tensor> chk) {
+               c10::optional<at::Tensor> chk, c10::optional<at::Tensor> wfc_pk) {
   DPA_CHECK_INPUT(y2); DPA_CHECK_INPUT(wfc); DPA_CHECK_INPUT(logits); DPA_CHECK_INPUT(p2); DPA_CHECK_INPUT(target);
   DPA_CHECK_INPUT(bfc); DPA_CHECK_INPUT(idx2); DPA_CHECK_INPUT(xh2); DPA_CHECK_INPUT(dlog);
   const int B = (int)y2.size(0), N = (int)wfc.size(0);
@@ -407,9 +436,22 @@ void head_step(at::Tensor y2, at::Tensor fslab2, at::Tensor fstats2, at::Tensor 
     const int ntl = N <= 10 ? nt : 256;
     auto kern = N > 10 ? head_row_kernel<T, NMAX, 256>
                        : (nt == 256 ? head_row_kernel<T, 10, 256> : head_row_kernel<T, 10, NT_MAX>);
+    const T* pkp = nullptr;
+    if (wfc_pk.has_value()) {  // the fc weights packed by this step's conv1 launch (cb::pack_fc)
+      DPA_CHECK_INPUT(*wfc_pk);
+      if constexpr (sizeof(T) == 2) {
+        TORCH_CHECK(ntl == 256, "head_step: packed fc weights go with the 256-lane kernel");
+        TORCH_CHECK(wfc_pk->scalar_type() == y2.scalar_type() && wfc_pk->numel() == cb::fcp_len(cb::fcp_nm(N)),
+                    "head_step: wfc_pk holds [256][", cb::fcp_nm(N), "][8] elements of the compute dtype");
+        pkp = dptr<T>(*wfc_pk);
+        kern = N > 10 ? head_row_kernel<T, NMAX, 256, true> : head_row_kernel<T, 10, 256, true>;
+      } else {
+        TORCH_CHECK(false, "head_step: packed fc weights are bf16 / fp16 only");
+      }
+    }
     hipLaunchKernelGGL(kern, dim3(B), dim3(ntl), 0, cur_stream(), dptr<T>(y2), bp, wfc.data_ptr<float>(),
                        bfc.data_ptr<float>(), dptr<T>(logits), dptr<T>(p2), idx2.data_ptr<uint8_t>(), dptr<T>(xh2), B,
-                       N, hr);
+                       N, hr, pkp);
   });
   DPA_CHECK_LAUNCH();
 }
@@ -418,7 +460,14 @@ void head_step(at::Tensor y2, at::Tensor fslab2, at::Tensor fstats2, at::Tensor 
 
 void register_convnet_head(pybind11::module& m) {
   auto s = m.def_submodule("convnet_head", "ConvNet head: forward + loss + backward in one launch");
-  s.def("head_step", &cnh::head_step);
+  namespace py = pybind11;
+  // wfc_pk (trailing, optional): the packed fc weights (None: the kernel reads fc.weight itself)
+  s.def("head_step", &cnh::head_step, py::arg("y2"), py::arg("fslab2"), py::arg("fstats2"), py::arg("g2"),
+        py::arg("b2"), py::arg("rm2"), py::arg("rv2"), py::arg("nbt2"), py::arg("momentum"), py::arg("eps"),
+        py::arg("wfc"), py::arg("bfc"), py::arg("logits"), py::arg("p2"), py::arg("idx2"), py::arg("xh2"),
+        py::arg("target"), py::arg("ignore_index"), py::arg("smoothing"), py::arg("scale"), py::arg("state"),
+        py::arg("loss"), py::arg("dlog"), py::arg("dls"), py::arg("dp2"), py::arg("bsum_rows"), py::arg("xc"),
+        py::arg("chk"), py::arg("wfc_pk") = py::none());
   s.def("supported", &cnh::supported);
   s.def("resident", &cnh::resident);
   DPA_DEF_STAMP_FNS(s);

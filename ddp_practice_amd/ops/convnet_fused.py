@@ -3,7 +3,8 @@
 Fusing across the layer boundaries of /root/reference/origin_main.py:9-31
 removes launches that exist only because torch runs one module at a time:
 
-  forward  (train): conv1(+BN1 sums, packs conv2's bf16 weight tiles) | BN1-ReLU-pool1 -> conv2 (+BN2 sums)
+  forward  (train): conv1(+BN1 sums, packs conv2's bf16 weight tiles and the head's fc weights)
+                    | BN1-ReLU-pool1 -> conv2 (+BN2 sums)
                     | BN2-ReLU-pool2 -> fc
                     = 3 launches for the model (per-layer ops: 6, torch: ~14 + host syncs)
   backward:         fc bwd (+BN2 sums) | {BN2 bwd -> conv2 dgrad (+BN1 sums), BN2 bwd -> conv2 wgrad}
@@ -101,6 +102,9 @@ class PreCE:
 
 _HEAD_OK: dict = {}
 _HEAD_SPEC = os.environ.get("DPA_HEAD_SPEC", "1") != "0"  # 0: no speculative head backward (A/B)
+# the conv1 launch packs fc.weight (compute dtype, lane-major granules) for the one-launch head,
+# whose 32 workgroups otherwise each load and round it; DPA_HEAD_PACK=0: the unpacked head (A/B)
+_HEAD_PACK = os.environ.get("DPA_HEAD_PACK", "1") != "0"
 
 
 def _head_step_ok(B: int, N: int, dtype: torch.dtype) -> bool:
@@ -151,12 +155,23 @@ class ConvNetFn(torch.autograd.Function):
             p2 = torch.empty((B, 32 * 49), dtype=cdtype, device=dev)
             idx2 = torch.empty((B, 32 * 49), dtype=torch.uint8, device=dev)
             xh2 = torch.empty((B, 32 * 49), dtype=cdtype, device=dev)
+            head_step = labels is not None and state is not None and _head_step_ok(B, N, cdtype)
+            # fc.weight packed for the one-launch head by the conv1 launch, read by the head of this
+            # same forward: never carried across steps (the weights change every step).  bf16 / fp16,
+            # 256-lane head only, and only where no launch of the step exchanges SyncBN sums
+            # in-kernel (xc): the launches that ranks sharing a card must fit together stay as
+            # they were.
+            wfc_pk = None
+            if (_HEAD_PACK and head_step and xc is None and cdtype != torch.float32
+                    and os.environ.get("DPA_HEAD_NT") != "1024"):
+                wfc_pk = torch.empty(cn.FCP_LANES * (16 if N > 10 else 10) * 8, dtype=cdtype, device=dev)
+            fcp = (wfc, wfc_pk) if wfc_pk is not None else (None, None)
             if gather is not None:  # the batch gather runs inside conv1 (data/loader.py defer=True)
                 imgs, lbls, order, ctr, lab_out, gsc, gsh = gather
                 cn.conv1_fwd_pack_gather(x, w1, b1, y1, fslab1, fstats1, rm1, w2, wpk_f, wpk_d, imgs, lbls, order,
-                                         ctr, lab_out, gsc, gsh)
+                                         ctr, lab_out, gsc, gsh, *fcp)
             else:
-                cn.conv1_fwd_pack(x, w1, b1, y1, fslab1, fstats1, rm1, w2, wpk_f, wpk_d)
+                cn.conv1_fwd_pack(x, w1, b1, y1, fslab1, fstats1, rm1, w2, wpk_f, wpk_d, *fcp)
             if sync and xc is None:
                 comm.all_reduce_(fslab1)
             cn.conv2_fwd(y1, fslab1, fstats1, g1, be1, rm1, rv1, nbt1, m1, e1, True, w2, b2, y2, fslab2, fstats2,
@@ -165,7 +180,7 @@ class ConvNetFn(torch.autograd.Function):
                 comm.all_reduce_(fslab2)
             ctx.spec = None
             ctx.chk = ctx.chk_scale = None
-            if labels is not None and state is not None and _head_step_ok(B, N, cdtype):
+            if head_step:
                 # labels known now (paired by the device loader): head forward + loss (+ the head
                 # backward when a GradScaler will seed it with its scale) in one launch
                 from .head import seed_scale
@@ -202,11 +217,13 @@ class ConvNetFn(torch.autograd.Function):
                     ctx.chk, ctx.chk_scale = chk, (scale if chk is not None else None)
                     _load_ext().convnet_head.head_step(
                         y2, fslab2, fstats2, g2, be2, rm2, rv2, nbt2, m2, e2, wfc, bfc, logits, p2, idx2, xh2, labels,
-                        int(ce_cfg[0]), float(ce_cfg[1]), scale, state, loss_buf, dlog, dls, dp2, bsum2, xc, chk)
+                        int(ce_cfg[0]), float(ce_cfg[1]), scale, state, loss_buf, dlog, dls, dp2, bsum2, xc, chk,
+                        wfc_pk)
                 else:
                     _load_ext().convnet_head.head_step(
                         y2, fslab2, fstats2, g2, be2, rm2, rv2, nbt2, m2, e2, wfc, bfc, logits, p2, idx2, xh2, labels,
-                        int(ce_cfg[0]), float(ce_cfg[1]), None, state, loss_buf, dlog, None, None, None, xc, None)
+                        int(ce_cfg[0]), float(ce_cfg[1]), None, state, loss_buf, dlog, None, None, None, xc, None,
+                        wfc_pk)
                 ctx.spec = spec
                 if holder is not None:
                     holder["ce"] = PreCE(labels, int(ce_cfg[0]), float(ce_cfg[1]), scale, loss_buf, dlog, dls)

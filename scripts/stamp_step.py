@@ -86,7 +86,9 @@ wrap(C.convnet_head, "head_step", lambda a: [("head_step", slice(0, 32))])
 wrap(C.convnet, "conv2_bwd", lambda a: [("conv2_bwd/dgrad", slice(0, NDG)),
                                          ("conv2_bwd/wgrad", slice(NDG, NDG + 4 * B))])
 for _n in ("conv1_fwd_pack_gather", "conv1_fwd_pack"):
-    wrap(C.convnet, _n, lambda a: [("conv1/conv", slice(0, 4 * B)), ("conv1/pack", slice(4 * B, 512))])
+    # behind the conv workgroups: 26 that pack the conv2 weights, then those that pack fc.weight
+    wrap(C.convnet, _n, lambda a: [("conv1/conv", slice(0, 4 * B)), ("conv1/pack", slice(4 * B, 4 * B + 26)),
+                                   ("conv1/fc pack", slice(4 * B + 26, 512))])
 wrap(C.convnet, "conv2_fwd", lambda a: [("conv2_fwd", slice(0, NFW))])
 wrap(C.convnet, "conv1_wgrad_slab2", lambda a: [("wgrad1_slab2/wgrad", slice(0, 7 * B)),
                                                  ("wgrad1_slab2/sums", slice(7 * B, 512))])
