@@ -5,6 +5,9 @@
 #include <torch/extension.h>
 
 #include <atomic>
+#include <condition_variable>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -78,6 +81,9 @@ class XgmiComm {
   // floats) through the wide site with the positioned form; out = the global row
   void wide_probe(const at::Tensor& in, const at::Tensor& out, int nblk);
   long long max_elems() const { return max_elems_; }
+  // one- and two-shot all-reduces this rank's host has issued (debug_state prints the same)
+  long long oneshot_issued() const { return ar_calls_.load(std::memory_order_relaxed); }
+  long long twoshot_issued() const { return ts_calls_.load(std::memory_order_relaxed); }
 
  private:
   int rank_, world_, device_;
@@ -101,6 +107,17 @@ class XgmiComm {
   // launches attached to each site, one- / two-shot all-reduces and the last one's bytes
   mutable std::atomic<long long> site_calls_[kSites] = {};
   std::atomic<long long> ar_calls_{0}, ts_calls_{0}, ar_last_bytes_{0};
+  // debug_state's snapshot threads that are still copying out of this rank's device memory.  A
+  // caller with a short wait_s returns before its thread has ended; close() waits for them
+  // before it frees what they read -- for at most 10 s: a snapshot stuck on a wedged device
+  // must not hang close(), so that case is not covered.  Shared with the threads: it
+  // outlives *this.
+  struct SnapGate {
+    std::mutex m;
+    std::condition_variable cv;
+    int running = 0;
+  };
+  std::shared_ptr<SnapGate> snaps_ = std::make_shared<SnapGate>();
 };
 
 }  // namespace xgmi

@@ -38,6 +38,7 @@
 #include <c10/hip/HIPGuard.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 
@@ -73,6 +74,19 @@ struct Args {
 
 __device__ __forceinline__ unsigned long long granule(float v, uint32_t ep) {
   return ((unsigned long long)ep << 32) | (unsigned long long)__float_as_uint(v);
+}
+
+// The average's one multiply, acc * s with s the fp32 1/W, as the fp32 product it is written as.
+// Without the empty asm the compiler fuses the multiply and the conversion to fp16 into one
+// v_fma_mixlo_f16, which rounds the EXACT product once, to fp16: an average on an fp16 tie
+// (frequent: the inputs are fp16 values) then came out one fp16 ulp away from the documented
+// fp32 multiply followed by one rounding to the storage type.
+template <int OP>
+__device__ __forceinline__ float scaled(float acc, float s) {
+  if (OP != 1) return acc;
+  float m = acc * s;
+  asm("" : "+v"(m));
+  return m;
 }
 
 // op: 0 sum, 1 avg, 2 max, 3 min
@@ -177,13 +191,15 @@ __global__ __launch_bounds__(kThreads) void oneshot_kernel(Args a) {
       f32x4 raw;
       T* r = reinterpret_cast<T*>(&raw);
 #pragma unroll
-      for (int j = 0; j < kPerThread; ++j) r[j] = Cvt<T>::from_f(acc[j] * s);
+      for (int j = 0; j < kPerThread; ++j) r[j] = Cvt<T>::from_f(scaled<OP>(acc[j], s));
       *reinterpret_cast<f32x4*>(out) = raw;
     } else if (ne == kPerThread) {
-      reinterpret_cast<f32x4*>(out)[0] = f32x4{acc[0] * s, acc[1] * s, acc[2] * s, acc[3] * s};
-      reinterpret_cast<f32x4*>(out)[1] = f32x4{acc[4] * s, acc[5] * s, acc[6] * s, acc[7] * s};
+      reinterpret_cast<f32x4*>(out)[0] = f32x4{scaled<OP>(acc[0], s), scaled<OP>(acc[1], s), scaled<OP>(acc[2], s),
+                                                 scaled<OP>(acc[3], s)};
+      reinterpret_cast<f32x4*>(out)[1] = f32x4{scaled<OP>(acc[4], s), scaled<OP>(acc[5], s), scaled<OP>(acc[6], s),
+                                                 scaled<OP>(acc[7], s)};
     } else {
-      for (int j = 0; j < ne; ++j) out[j] = Cvt<T>::from_f(acc[j] * s);
+      for (int j = 0; j < ne; ++j) out[j] = Cvt<T>::from_f(scaled<OP>(acc[j], s));
     }
   }
   // 3. this block's epoch is done (after every lane read the counter)
@@ -355,7 +371,7 @@ __global__ __launch_bounds__(kThreads) void twoshot_kernel(TSArgs a) {
     }
     if (!ok) break;
 #pragma unroll
-    for (int j = 0; j < kPerThread; ++j) acc[j] = Cvt<T>::to_f(Cvt<T>::from_f(acc[j] * s));
+    for (int j = 0; j < kPerThread; ++j) acc[j] = Cvt<T>::to_f(Cvt<T>::from_f(scaled<OP>(acc[j], s)));
     for (int i = 1; i < a.world; ++i) {
       const int p = (a.rank + i) % a.world;
       push8(reinterpret_cast<unsigned long long*>(a.peers.base[p] + par + rs_bytes +
@@ -453,6 +469,11 @@ XgmiComm::~XgmiComm() { close(); }
 
 void XgmiComm::close() {
   if (local_ == nullptr) return;
+  {  // a snapshot thread of debug_state may still be copying from the memory freed below: wait
+     // for it, bounded (after 10 s the memory is freed regardless, as before)
+    std::unique_lock<std::mutex> lk(snaps_->m);
+    snaps_->cv.wait_for(lk, std::chrono::seconds(10), [&] { return snaps_->running == 0; });
+  }
   c10::hip::HIPGuard guard(device_);
   (void)hipDeviceSynchronize();
   for (int p = 0; p < world_; ++p)
@@ -746,6 +767,11 @@ std::string XgmiComm::debug_state(double wait_s) const {
       for (int p = 0; p < world; ++p) goff.push_back(r.off + (long long)par * kMaxRanks * r.slot + (long long)p * r.slot);
   auto done = std::make_shared<std::promise<bool>>();
   auto fut = done->get_future();
+  auto gate = snaps_;
+  {
+    std::lock_guard<std::mutex> lk(gate->m);
+    ++gate->running;
+  }
   std::thread([=]() {
     bool ok = hipSetDevice(dev) == hipSuccess;
     hipStream_t st = nullptr;
@@ -759,7 +785,15 @@ std::string XgmiComm::debug_state(double wait_s) const {
         ok = hipMemcpyAsync(snap->tctr.data(), tctr, 4 * std::min(4, tsb), hipMemcpyDeviceToHost, st) == hipSuccess;
       ok = ok && hipStreamSynchronize(st) == hipSuccess;
     }
+    // the stream goes only after a clean synchronize: destroying one that failed or hangs can
+    // block in the runtime, and this thread must end (a failed snapshot leaks its stream)
+    if (st != nullptr && ok) (void)hipStreamDestroy(st);
     done->set_value(ok);
+    {
+      std::lock_guard<std::mutex> lk(gate->m);
+      --gate->running;
+    }
+    gate->cv.notify_all();
   }).detach();
   if (fut.wait_for(std::chrono::duration<double>(wait_s)) != std::future_status::ready) {
     o << "; device snapshot timed out after " << wait_s << " s";
@@ -913,6 +947,7 @@ void register_xgmi(pybind11::module& m) {
            py::arg("t"), py::arg("op") = "sum", py::arg("out") = py::none())
       .def("wide_probe", &xgmi::XgmiComm::wide_probe, py::arg("inp"), py::arg("out"), py::arg("nblk"))
       .def("debug_state", &xgmi::XgmiComm::debug_state, py::arg("wait_s") = 2.0)
+      .def("issued", [](const xgmi::XgmiComm& c) { return std::make_pair(c.oneshot_issued(), c.twoshot_issued()); })
       .def("site_probe", &xgmi::XgmiComm::site_probe, py::arg("site"), py::arg("inp"), py::arg("out"),
            py::arg("grid") = 1)
       .def("all_reduce_twoshot",

@@ -92,6 +92,7 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
   __shared__ float* sp1[MAXT];
   __shared__ float* sp2[MAXT];
   __shared__ int s_bad;
+  __shared__ int s_chk;  // XG: a lane of this workgroup read a set pre-check word
   __shared__ float spart[SLAB_G * (SLAB_CC + 1)];  // slab workgroups: row groups x (columns + 1)
   const int tid = threadIdx.x;
   const int n = L.n;
@@ -107,6 +108,7 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
     float* const a0 = L.p0[ti];
     float* const a1 = L.p1[ti];
     float* const a2 = L.p2[ti];
+    if (XG && tid == 0) s_chk = 0;
     if (tid <= n) soff[tid] = (int)co;
     if (tid < n) {
       snum[tid] = (int)nu;
@@ -147,8 +149,12 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
   const bool pre = chk != nullptr && cscale >= 1.f;  // uniform: every workgroup reads the same word
   // XG: a flagged rank pushes NaN in place of its values, so every peer's workgroup sees a
   // non-finite average of each element it owns and skips -- the ranks agree without a word
-  // exchange (the producers' bound keeps a sum of W checked values finite)
-  const bool poison = XG && pre && cbad;
+  // exchange (the producers' bound keeps a sum of W checked values finite).  The words are
+  // split over the lanes, so a lane's own cbad is not the rank's: the workgroup shares it
+  // through s_chk (cleared before the table barrier above, read after the epoch barrier
+  // below) -- with the lane's own flag only the lanes that happened to read a set word pushed
+  // NaN, and a peer's workgroup none of whose lanes met one applied its update alone.
+  if (XG && pre && cbad) s_chk = 1;
   const float nanf_ = __int_as_float(0x7fc00000);
   auto load4 = [](const float* p, int rem) {
     if (rem >= 4) return *reinterpret_cast<const f32x4*>(p);
@@ -228,6 +234,7 @@ amp_sgd_body(const MTList& L, float* __restrict__ scale, int* __restrict__ track
     __syncthreads();
 #endif
     const uint32_t ep = ep_x;
+    const bool poison = pre && s_chk != 0;  // uniform in the workgroup
     xgmi::xsite_advance(xg, ep, bid, THR);
     const long long par = (long long)(ep & 1u) * xgmi::kMaxRanks * xg.slot_bytes;
     auto gran = [ep](float v) { return ((unsigned long long)ep << 32) | (unsigned long long)__float_as_uint(v); };

@@ -215,6 +215,16 @@ def normal(sizes, seed, scale=1024.0):
     return [r(n) for n in sizes], [r(n) * scale for n in sizes], [r(n) * 0.1 for n in sizes]
 
 
+def slab_rows(col_sums, rows, seed, scale=1024.0):
+    """A [rows][n] slab (the fused step's slab source) of dyadic values, multiples of scale / 8,
+    whose column sums are ``col_sums`` (dyadic too) exactly in whatever order they are added."""
+    gen = torch.Generator().manual_seed(seed)
+    slab = torch.stack([_k8(col_sums.numel(), gen) * scale for _ in range(rows)])
+    slab[rows - 1] = col_sums - slab[:rows - 1].sum(0)
+    assert torch.equal(slab.double().sum(0), col_sums.double())
+    return slab.contiguous()
+
+
 # ------------------------------------------------------------------------------ scale table
 # (scale, tracker, found, growth, backoff, interval): torch._amp_update_scale_'s branches
 SCALE_TABLE = [

@@ -9,6 +9,8 @@ from datetime import timedelta
 import torch
 import torch.distributed  # noqa: F401  (TCPStore)
 
+from . import _xgmi_ref as X
+
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 
 
@@ -17,14 +19,18 @@ def _data(rank, n, dt, it):
     return torch.randn(n, generator=g).to(dt)
 
 
+def _ref(world, n, dt, it, op):
+    """The engine's contract, bit for bit (tests/_xgmi_ref.py): rank-ordered fp32 accumulation, one
+    multiply by fp32 1/W, one rounding to the storage type."""
+    return X.reduce([_data(r, n, dt, it) for r in range(world)], op, dt)
+
+
 def _expect(world, n, dt, it, op):
-    xs = [_data(r, n, dt, it).float() for r in range(world)]
-    acc = xs[0].clone()
-    for x in xs[1:]:
-        acc = torch.maximum(acc, x) if op == "max" else torch.minimum(acc, x) if op == "min" else acc + x
-    if op == "avg":
-        acc = acc / world
-    return acc
+    return _ref(world, n, dt, it, op).float()
+
+
+def _bits(got, world, n, dt, it, op, what):
+    X.assert_bits(got, _ref(world, n, dt, it, op), what)
 
 
 def _check(got, exp, dt, what):
@@ -65,6 +71,7 @@ def worker(rank, world, port, mode, q):
                 exp = _expect(world, n, torch.float32, it, "sum")
                 for b in range(4):
                     _check(o[b * n:(b + 1) * n], exp, torch.float32, ("site", it, b))
+                    _bits(o[b * n:(b + 1) * n], world, n, torch.float32, it, "sum", ("site", it, b))
                 out[f"site{it}"] = o.cpu().numpy().tobytes()
             t = torch.zeros(64, device=dev)
             o = torch.empty(2 * 64, device=dev)
@@ -85,6 +92,8 @@ def worker(rank, world, port, mode, q):
                 exp = _expect(world, 64, torch.float32, 100 + r, "sum")
                 _check(o[:64], exp, torch.float32, ("site graph", r))
                 _check(o[64:], exp, torch.float32, ("site graph", r))
+                for half in (o[:64], o[64:]):
+                    _bits(half, world, 64, torch.float32, 100 + r, "sum", ("site graph", r))
             store.set(f"done{rank}", "1")
             store.wait([f"done{r}" for r in range(world)])
             x.close()
@@ -105,6 +114,7 @@ def worker(rank, world, port, mode, q):
                 torch.cuda.synchronize()
                 assert x.error() == 0, x.error_string()
                 _check(o, _expect(world, n, torch.float32, it, "sum"), torch.float32, ("wide", it, n, nb))
+                _bits(o, world, n, torch.float32, it, "sum", ("wide", it, n, nb))
                 out[f"wide{it}"] = o.cpu().numpy().tobytes()
             t = torch.zeros(4097, device=dev)
             o = torch.empty(4097, device=dev)
@@ -128,7 +138,9 @@ def worker(rank, world, port, mode, q):
                 torch.cuda.synchronize()
                 assert x.error() == 0, x.error_string()
                 _check(o, _expect(world, 4097, torch.float32, 200 + r, "sum"), torch.float32, ("wide graph", r))
+                _bits(o, world, 4097, torch.float32, 200 + r, "sum", ("wide graph", r))
                 _check(o2, _expect(world, 257, torch.float32, 300 + r, "sum"), torch.float32, ("wide graph 2", r))
+                _bits(o2, world, 257, torch.float32, 300 + r, "sum", ("wide graph 2", r))
                 out[f"wg{r}"] = o.cpu().numpy().tobytes()
             store.set(f"done{rank}", "1")
             store.wait([f"done{r}" for r in range(world)])
@@ -154,6 +166,7 @@ def worker(rank, world, port, mode, q):
                 torch.cuda.synchronize()
                 assert x.error() == 0, x.error_string()
                 _check(o, _expect(world, n, dt, it, op), dt, ("twoshot", n, dn, op))
+                _bits(o, world, n, dt, it, op, ("twoshot", n, dn, op))
                 out[f"ts{it}"] = o.float().cpu().numpy().tobytes()
                 it += 1
             xc = C.xgmi.XgmiCollective(x)
@@ -163,6 +176,7 @@ def worker(rank, world, port, mode, q):
                 torch.cuda.synchronize()
                 assert x.error() == 0, x.error_string()
                 _check(t, _expect(world, n, torch.float32, it, "sum"), torch.float32, ("collective", n))
+                _bits(t, world, n, torch.float32, it, "sum", ("collective", n))
                 it += 1
             a = torch.zeros(1 << 21, device=dev)
             b = torch.zeros(5 << 20, dtype=torch.bfloat16, device=dev)
@@ -184,7 +198,9 @@ def worker(rank, world, port, mode, q):
                 torch.cuda.synchronize()
                 assert x.error() == 0, x.error_string()
                 _check(a, _expect(world, 1 << 21, torch.float32, it, "sum"), torch.float32, ("ts graph a", r))
+                _bits(a, world, 1 << 21, torch.float32, it, "sum", ("ts graph a", r))
                 _check(b, _expect(world, 5 << 20, torch.bfloat16, it + 1, "avg"), torch.bfloat16, ("ts graph b", r))
+                _bits(b, world, 5 << 20, torch.bfloat16, it + 1, "avg", ("ts graph b", r))
                 it += 2
             store.set(f"done{rank}", "1")
             store.wait([f"done{r}" for r in range(world)])
@@ -253,6 +269,7 @@ def worker(rank, world, port, mode, q):
             torch.cuda.synchronize()
             assert x.error() == 0, x.error_string()
             _check(t, _expect(world, n, dt, it, op), dt, (n, dn, op))
+            _bits(t, world, n, dt, it, op, (n, dn, op))
             out[f"{n}{dn}{op}"] = t.float().cpu().numpy().tobytes()
             it += 1
         # back-to-back reuse of the same slots (parity flips, epochs advance), out of place
@@ -262,6 +279,7 @@ def worker(rank, world, port, mode, q):
             o = torch.empty_like(t)
             x.all_reduce(t, "sum", o)
             _check(o.cpu() if k % 7 else o, _expect(world, n, torch.float32, it, "sum"), torch.float32, ("loop", k))
+            _bits(o, world, n, torch.float32, it, "sum", ("loop", k))
             it += 1
         torch.cuda.synchronize()
         assert x.error() == 0, x.error_string()
@@ -275,6 +293,7 @@ def worker(rank, world, port, mode, q):
             torch.cuda.synchronize()
             assert x.error() == 0, x.error_string()
             _check(t, _expect(world, n, dt, it, op), dt, ("chunked", n, dn, op))
+            _bits(t, world, n, dt, it, op, ("chunked", n, dn, op))
             out[f"chunked{n}{dn}{op}"] = t.float().cpu().numpy().tobytes()
             it += 1
         # hipGraph: capture two collectives, replay with fresh inputs each time
@@ -298,7 +317,9 @@ def worker(rank, world, port, mode, q):
             torch.cuda.synchronize()
             assert x.error() == 0, x.error_string()
             _check(a, _expect(world, 4099, torch.float32, it, "sum"), torch.float32, ("graph a", r))
+            _bits(a, world, 4099, torch.float32, it, "sum", ("graph a", r))
             _check(b, _expect(world, 70000, torch.float32, it + 1, "max"), torch.float32, ("graph b", r))
+            _bits(b, world, 70000, torch.float32, it + 1, "max", ("graph b", r))
             it += 2
         store.set(f"done{rank}", "1")
         store.wait([f"done{r}" for r in range(world)])

@@ -6,7 +6,8 @@ inputs, per element within the counted bound on floats.
   a  unscale_check   CHUNK edges, batch splits (37 / 73 tensors), one non-finite at a time
   b  sgd_step        the option grid, first flags across batches, found_inf, grad_scale, lr_dev
   c  update_scale    torch._amp_update_scale_'s table, found_inf re-armed
-  d  amp_sgd_fused   36 tensors; a grid of one, U = 1 / 2 / 4; plain mode; pre-checked mode
+  d  amp_sgd_fused   36 tensors; a grid of one, U = 1 / 2 / 4; plain mode; pre-checked mode; the
+                     slab source (with a peer: tests/test_xgmi_exact_gpu.py)
   e  amp_sgd_large   1 / 37 / 512 tensors, the table reused eager and graph-replayed
   f  flat_copy       both directions, gaps, s = 0.5 and 1/3
 
@@ -517,6 +518,46 @@ def test_fused_prechecked_mode(C):
     t, i = fused_places(sizes)[1]
     ref = run(_words([0, 0, 0], 0.5), grads=_inject(g, t, i, INF), sync_step=1)
     assert ref["found"] and float(st.scale) == 512.0
+
+
+SLAB_SIZES = [7, 33, 1023, 1025, 36]
+
+
+@pytest.mark.parametrize("amp", [True, False], ids=["amp", "plain"])
+@pytest.mark.parametrize("rows", [5, 37])
+def test_fused_slab_source(C, rows, amp):
+    """The slab source: the last tensor's gradient is not in memory but the column sums of a
+    [rows][36] slab, summed by three extra workgroups (16 columns each, the last with 4; 5 rows
+    leave most of the 16 row groups empty, 37 give some three rows).  Dyadic rows whose sums are
+    the dyadic gradient, so any association is exact: the step is bitwise the step fed the
+    pre-summed gradient, which is bitwise _sgd_ref's.  The region itself is written, never read."""
+    sizes = SLAB_SIZES
+    h = R.options(R.DYADIC, True, True, False, False, True)
+    first = [1, 0, 1, 0, 0]
+    sc = 1024.0 if amp else 1.0
+    st = State(sizes)
+    p, g, b = R.dyadic(sizes, 27 + rows, scale=sc)
+
+    def launch(**kw):
+        C.optim.amp_sgd_fused(st.P.views, st.G.views, st.B.views, h["lr"], h["momentum"], h["dampening"],
+                              h["weight_decay"], h["nesterov"], h["maximize"], first, st.scale if amp else None,
+                              st.tracker if amp else None, st.found if amp else None, 2.0, 0.5, 2, st.sync, None, **kw)
+
+    st.load(p, g, b, scale=sc)
+    _run(st, launch, True, "amp_sgd_fused (slab)", first=first, amp=amp, sync_step=int(amp), **h)
+    want, want_s = st.read(), (float(st.scale), int(st.tracker))
+    slab = R.slab_rows(g[4], rows, 28 + rows, sc).to(DEV)
+    st.load(p, g[:4] + [torch.full((36,), 12345.0)], b, scale=sc)
+    s0 = int(st.sync[0])
+    launch(slab=slab, slab_out=st.G.views[4])
+    torch.cuda.synchronize()
+    st.check_pads()
+    got = st.read()
+    for key in ("p", "g", "b"):
+        for i, (x, w) in enumerate(zip(got[key], want[key])):
+            same_bits(x, w, f"slab rows={rows}: {NAMES[key]}[{i}] vs the pre-summed step")
+    assert (float(st.scale), int(st.tracker)) == want_s
+    assert int(st.sync[0]) == s0 + int(amp) and int(st.sync[3]) == 0  # 3 + 3 workgroups: one barrier generation
 
 
 # =============================================================================== e
