@@ -32,13 +32,20 @@ __host__ __device__ constexpr int conv5x5_win_rows(int H, int W, int nsplit, boo
   return mx;
 }
 
-// Epilogue of the data-grad kernel that produces a pooled grad: per-workgroup
-// BN partial sums of the block below ([S1 | S2] per channel -> one slab row).
+// Epilogue of the data-grad kernel that produces a pooled grad: BN partial sums of the block
+// below, [S1 | S2] per channel, one slab row per QUARTER of an image, whatever the launch's split.
+// Quarter k of an image is the m-tiles [MT*k/4, MT*(k+1)/4) (at most 4), the range of workgroup k
+// of a 4-way split; a workgroup of a 2-way split covers exactly two of them and writes both rows.
+// Within a quarter the m-tile mt has slot mt - quarter start.  A slot's partial is what one wave
+// produces for that one m-tile (the lane's 4 pixels added in order from zero, then xor16_sum /
+// xor32_sum); the row is the slots' partials added in slot order from 0.f.  Either split builds
+// every row by exactly these operations, so the slab's 4 * B rows are the same bit for bit.
+constexpr int EPI_QUARTERS = 4;
 template <typename T>
 struct BwdEpi {
   const uint8_t* idx;  // that block's pooled index (relu bit)
   const T* xh;         // that block's xhat at the argmax
-  float* bslab;        // rows = workgroups, row = [S1(COUT) | S2(COUT)]
+  float* bslab;        // [EPI_QUARTERS * B] rows, row 4 b + k = [S1(COUT) | S2(COUT)] of quarter k of image b
 };
 
 // ---------------------------------------------------------------------------
@@ -187,8 +194,10 @@ struct GatherIn {
 //          argmax for the backward (split 0);
 //   PRO 2: (MODE 2) the input dy is produced from the pooled grad of the next
 //          block (bin: backward through MaxPool -> ReLU -> BN, see BwdIn).
-//   EPI 1: (MODE 2) the output is a pooled grad: also write this workgroup's
-//          BN partial sums [S1 | S2] of the block below (epi).
+//   EPI 1: (MODE 2) the output is a pooled grad: also write the BN partial sums [S1 | S2] of
+//          the block below, one row per image quarter this workgroup covers (epi, BwdEpi).
+//          ES: the launch's nsplit at compile time, 2 or 4 (the epilogue's register and LDS
+//          shapes follow from the quarters per workgroup).
 //   WPK 0: stage the weight tile from the f32 master weights w;
 //   WPK 1: w is ignored, the tile is copied from the pre-packed wpk (pack_w2);
 //   WPK 2: (CIN 1, PRO 0 / 3) as 0 with every load of the prologue issued before the first
@@ -215,7 +224,7 @@ __host__ __device__ constexpr size_t conv5x5_dyn_bytes() {
 // launch's nsplit: the launcher checks it); the per-lane trip counts of the staging pass and
 // its register arrays follow from it.  WR = H: every workgroup stages the whole image.
 template <typename T, int CIN, int COUT, int H, int W, int MODE, int PRO = 0, int EPI = 0, int WPK = 0,
-          bool DYN = false, int WR = H>
+          bool DYN = false, int WR = H, int ES = 0>
 __device__ __forceinline__ void
 conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
              T* __restrict__ y, float* __restrict__ fslab, float* __restrict__ fstats,
@@ -228,6 +237,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   static_assert(PRO != 2 || MODE == 2, "PRO 2 is a data-grad prologue");
   static_assert(PRO != 3 || (CIN == 1 && MODE != 2), "PRO 3 gathers single-channel input images");
   static_assert(EPI == 0 || MODE == 2, "EPI 1 is a data-grad epilogue");
+  static_assert(EPI == 0 ? ES == 0 : (ES == 2 || ES == 4), "EPI 1: a 2-way or a 4-way split, known at compile time");
   constexpr int NCH = CIN >= 8 ? CIN / 8 : 1;              // 16-B groups per pixel
   constexpr int HP = H + 4, WPD = W + 4;
   constexpr int K = 25 * CIN;
@@ -263,7 +273,24 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
       return px * CIN + ((((c >> 3) ^ ((px / PPB) & (NCH - 1)))) << 3) + (c & 7);
     }
   };
-  __shared__ float lstat[(NTHR / 64) * 2 * COUT];
+  // EPI 1: NQ quarters per workgroup, each with up to NTHR / 64 slots (BwdEpi)
+  constexpr int NQ = EPI == 1 ? EPI_QUARTERS / ES : 1;
+  static_assert(EPI == 0 || (MT + EPI_QUARTERS - 1) / EPI_QUARTERS <= NTHR / 64,
+                "EPI 1: a quarter has at most one m-tile per wave");
+  // the per-(quarter, wave / slot) partials of the statistics epilogue.  PRO 2's reduction scratch
+  // (part: bn_bwd_coef) is dead from the compute barrier on, so the two-quarter epilogue keeps its
+  // partials there and a 2-way data-gradient workgroup's static LDS does not grow with them
+  // (it shrinks by the 512 B of lstat_s).  The assert below covers the size; the LIFETIME is a
+  // rule of this body: nothing may read or write `part` after the compute barrier (its last use
+  // is inside bn_bwd_coef, see the note there), and lstat is first written after the MFMA loop.
+  // Instantiations that use neither array declare it with one float, which the compiler drops
+  // (their LDS sizes are the parent's: profiles/dgrad_rows_ab.txt, resources)
+  constexpr int LSN = NQ * (NTHR / 64) * 2 * COUT;
+  constexpr bool LS_IN_PART = PRO == 2 && NQ > 1;
+  static_assert(!LS_IN_PART || LSN <= NTHR, "EPI 1: the partials fit the reduction scratch");
+  __shared__ float part_s[PRO == 2 ? NTHR : 1];
+  __shared__ float lstat_s[LS_IN_PART ? 1 : LSN];
+  float* const lstat = LS_IN_PART ? part_s : lstat_s;
 
   const int tid = threadIdx.x;
   const int b = bid / nsplit;
@@ -650,7 +677,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
     }
   } else {
     __shared__ float coef[5 * CIN], sums[2 * CIN];
-    __shared__ float part[NTHR];
+    float* const part = part_s;
     // the stages produce the windows of rows [r_lo, r_lo + SR) (h: relative to r_lo); this
     // workgroup's are the first r_n (even) of them
     if constexpr (CIN % 8 == 0 && sizeof(T) == 2) {
@@ -706,9 +733,18 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   const int lane = tid & 63, wv = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
 
-  float s1[NT], s2[NT];
+  // statistics accumulators: one pair per quarter with EPI 1 (sq: the slot of the m-tile this
+  // wave met in the quarter, -1: none -- a wave meets at most one, its m-tiles lie NTHR / 64 apart)
+  float s1[NQ][NT], s2[NQ][NT];
+  int sq[NQ];
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt) s1[nt] = s2[nt] = 0.f;
+  for (int k = 0; k < NQ; ++k) {
+    sq[k] = -1;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) s1[k][nt] = s2[k][nt] = 0.f;
+  }
+  // EPI 1, two quarters: this workgroup's second quarter starts at m-tile qmid
+  const int qmid = NQ == 2 ? (MT * (2 * sp + 1)) / EPI_QUARTERS : mt1;
 
   for (int mt = mt0 + wv; mt < mt1; mt += NTHR / 64) {
     const int m = mt * 16 + r;
@@ -743,6 +779,10 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
     }
     // --- epilogue: D[row = 4q+i][col = r] -> pixel mt*16+4q+i, channel nt*16+r
     const int pix0 = mt * 16 + 4 * q;
+    // EPI 1: this m-tile's sums start at zero (e1, e2) and become its quarter's accumulators
+    float e1[NT], e2[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) e1[nt] = e2[nt] = 0.f;
     if (pix0 < HW) {
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
@@ -756,40 +796,85 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
           dst[i] = Cvt<T>::from_f(v);
           if (MODE == 0) {
             const float d = rnd_t<T>(v) - sh;
-            s1[nt] += d;
-            s2[nt] += d * d;
+            s1[0][nt] += d;
+            s2[0][nt] += d * d;
           }
           if (EPI == 1) {
             const int le = co * EPIX + pix0 - mt0 * 16 + i;
             const float g = (eidx[le] & IDX_RELU) ? rnd_t<T>(v) : 0.f;
-            s1[nt] += g;
-            s2[nt] += g * Cvt<T>::to_f(exh[le]);
+            e1[nt] += g;
+            e2[nt] += g * Cvt<T>::to_f(exh[le]);
           }
+        }
+      }
+    }
+    if constexpr (EPI == 1) {  // (selects, wave-uniform: no indexed registers)
+      const bool second = mt >= qmid;
+#pragma unroll
+      for (int k = 0; k < NQ; ++k) {
+        const bool mine = second == (k == 1);
+        sq[k] = mine ? mt - (k == 1 ? qmid : mt0) : sq[k];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          s1[k][nt] = mine ? e1[nt] : s1[k][nt];
+          s2[k][nt] = mine ? e2[nt] : s2[k][nt];
         }
       }
     }
   }
   DPA_STAMP(6);
   if constexpr (MODE == 0 || EPI == 1) {
+    // partial (k, j) of the workgroup: MODE 0 (k = 0) wave j's; EPI 1 slot j's of its quarter k.
+    // Every lane sum first, the masked stores behind them: the quarters' permlane chains are
+    // independent and overlap (with the stores in between, each quarter's chain waited for the one
+    // before it behind an exec change)
+    float a1[NQ][NT], a2[NQ][NT];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      // lanes r, r+16, r+32, r+48 (VALU permlane swaps, no LDS round trip; every lane active)
-      const float a1 = xor32_sum(xor16_sum(s1[nt])), a2 = xor32_sum(xor16_sum(s2[nt]));
-      if (q == 0) {  // per-wave partials, summed below in a fixed order (deterministic)
-        lstat[wv * 2 * COUT + nt * 16 + r] = a1;
-        lstat[wv * 2 * COUT + COUT + nt * 16 + r] = a2;
+    for (int k = 0; k < NQ; ++k) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        // lanes r, r+16, r+32, r+48 (VALU permlane swaps, no LDS round trip; every lane active)
+        a1[k][nt] = xor32_sum(xor16_sum(s1[k][nt]));
+        a2[k][nt] = xor32_sum(xor16_sum(s2[k][nt]));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+      const int j = EPI == 1 ? sq[k] : wv;
+      if (q == 0 && j >= 0) {  // summed below in a fixed order (deterministic)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          lstat[(k * (NTHR / 64) + j) * 2 * COUT + nt * 16 + r] = a1[k][nt];
+          lstat[(k * (NTHR / 64) + j) * 2 * COUT + COUT + nt * 16 + r] = a2[k][nt];
+        }
       }
     }
     __syncthreads();
-    float* row = (MODE == 0 ? fslab + (size_t)bid * fslab_row(COUT)
-                            : epi.bslab + (size_t)bid * 2 * COUT);
-    if (tid < 2 * COUT) {
-      float t = 0.f;
+    if constexpr (EPI == 1) {
+      // row 4 b + (this workgroup's first quarter + k): the quarter's slots in slot order from
+      // 0.f; a slot past the quarter's m-tiles was written by no wave: whatever its floats hold
+      // is loaded (all slots in one batch, one wait) and dropped, and it contributes the 0.f a
+      // wave without an m-tile would have stored
+      if (tid < NQ * 2 * COUT) {
+        const int k = tid / (2 * COUT), c = tid % (2 * COUT);
+        const int nsl = k == 0 ? qmid - mt0 : mt1 - qmid;
+        float v[NTHR / 64];
 #pragma unroll
-      for (int w2 = 0; w2 < NTHR / 64; ++w2) t += lstat[w2 * 2 * COUT + tid];
-      row[tid] = t;
+        for (int j = 0; j < NTHR / 64; ++j) v[j] = lstat[(k * (NTHR / 64) + j) * 2 * COUT + c];
+        float t = 0.f;
+#pragma unroll
+        for (int j = 0; j < NTHR / 64; ++j) t += j < nsl ? v[j] : 0.f;
+        epi.bslab[((size_t)b * EPI_QUARTERS + sp * NQ + k) * 2 * COUT + c] = t;
+      }
     }
     if constexpr (MODE == 0) {
+      float* row = fslab + (size_t)bid * fslab_row(COUT);
+      if (tid < 2 * COUT) {
+        float t = 0.f;
+#pragma unroll
+        for (int w2 = 0; w2 < NTHR / 64; ++w2) t += lstat[w2 * 2 * COUT + tid];
+        row[tid] = t;
+      }
       if (tid == 0) {
         const int p0 = mt0 * 16, p1 = min(mt1 * 16, HW);
         row[2 * COUT] = (float)(p1 - p0);
@@ -813,7 +898,8 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
   DPA_STAMP(7);
 }
 
-template <typename T, int CIN, int COUT, int H, int W, int MODE, int PRO = 0, int EPI = 0, int WPK = 0, int WR = H>
+template <typename T, int CIN, int COUT, int H, int W, int MODE, int PRO = 0, int EPI = 0, int WPK = 0, int WR = H,
+          int ES = 0>
 __global__ void __launch_bounds__(NTHR)
 conv5x5_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                T* __restrict__ y, float* __restrict__ fslab, float* __restrict__ fstats,
@@ -831,8 +917,8 @@ conv5x5_kernel(const T* __restrict__ x, const float* __restrict__ w, const float
       return;
     }
   }
-  conv5x5_body<T, CIN, COUT, H, W, MODE, PRO, EPI, WPK, false, WR>(x, w, bias, y, fslab, fstats, shift, nsplit, pin,
-                                                                   bin, epi, wpk, pk, (int)blockIdx.x, gin);
+  conv5x5_body<T, CIN, COUT, H, W, MODE, PRO, EPI, WPK, false, WR, ES>(x, w, bias, y, fslab, fstats, shift, nsplit,
+                                                                       pin, bin, epi, wpk, pk, (int)blockIdx.x, gin);
 }
 
 }  // namespace cb

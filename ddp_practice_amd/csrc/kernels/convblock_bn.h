@@ -373,6 +373,10 @@ __device__ __forceinline__ void colsum_rows(const float* __restrict__ src, int r
 // coef (LDS, 5C floats): [k1 | k2 | gi | mean | invstd]; part: >= blockDim.x
 // floats of LDS, sums: >= 2C floats of LDS.  Workgroup `leader` also writes
 // dgamma / dbeta from the local rows.  Ends with a barrier.
+// `part` is scratch of this function alone: its last use is the leader's second colsum_rows, which
+// ends with a barrier.  cb::conv5x5_body's 2-way data-gradient epilogue reuses the same floats for
+// its statistics partials after its compute barrier (conv5x5.h LS_IN_PART), so a caller must not
+// keep anything in `part` past that barrier.
 template <int C, typename T>
 __device__ __forceinline__ void bn_bwd_coef(const BwdIn<T>& bi, float* coef, float* part, float* sums, int bid) {
   const int tid = threadIdx.x;

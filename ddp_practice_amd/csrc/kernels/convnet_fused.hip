@@ -496,44 +496,75 @@ void conv1_fwd_pack_gather(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tenso
   DPA_CHECK_LAUNCH();
 }
 
-// Workgroups per image of the conv2 data gradient: 2 for bf16 / fp16, 4 for fp32, whose
-// 16x16x4 MFMA chains are 4x as long (profiles/r6bf_fp32_dgrad_split_ab.txt).
-// bf16 / fp16 at 4 measure FASTER on one GPU once the splits stage row windows (a quarter runs
-// one m-tile per wave: MFMA loop 2.0 -> 1.2 us; bf16 step 0.0409 -> 0.0402 ms with the forward
-// at 4, profiles/conv2_rowwin_ab.txt; staging the whole image it was +2.5 us, r6m_split_ab.txt),
-// but the merged backward launch then has 128 + 128 + 7 = 263 workgroups at batch 32, more
-// than sites_resident() accepts at 2 per CU (co_resident keeps one in reserve: 256), so SyncBN
-// would leave the in-kernel exchange for an all-reduce per sum, and two ranks sharing a card
-// would not fit it together.  It stays at 2 until that launch is smaller.
+// Workgroups per image of the conv2 data gradient, chosen per launch.
+// fp32: 4 everywhere; its 16x16x4 MFMA chains are 4x as long (profiles/r6bf_fp32_dgrad_split_ab.txt).
+// bf16 / fp16: 4 when the launch exchanges nothing in-kernel (xc null: one rank, or SyncBN
+// all-reduced between the launches), 2 when its site is active.  A quarter image per workgroup
+// runs one m-tile per wave (MFMA loop 2.0 -> 1.2 us, profiles/conv2_rowwin_ab.txt; the step:
+// profiles/dgrad_rows_ab.txt), but the merged backward launch then has 128 + 128 + 7 = 263
+// workgroups at batch 32, more than sites_resident() accepts at 2 per CU (co_resident keeps one
+// in reserve: 256), and two ranks sharing a card would not fit it together -- so a site launch
+// keeps the 2-way grid, LDS and occupancy it always had, and set_site_grid / site_grid_fits /
+// sites_resident speak of that grid (kDgradSiteSplitT).
+// The two kinds of launch still agree bit for bit: bslab1 has one row per image QUARTER
+// (cb::BwdEpi), 4 B rows built by the same operations at either split, so the consumer of the
+// rows (the conv1 weight gradient's bn_bwd_coef) cannot tell which launch wrote them.
 // The staging pass is one iteration per lane at 2 and at 4 (5 pooled rows x 7 x 4 channel
 // groups = 140 windows of 256 lanes): the window shortens no chain there, it removes loads.
-// Compile-time per dtype: the kernels take it as a constant (kDgradSplitT<T>), the host sizes
-// follow from the tensor dtype (dgrad_split).
-#ifndef DPA_DGRAD2_SPLIT
-#define DPA_DGRAD2_SPLIT 2
-#endif
-#ifndef DPA_DGRAD2_SPLIT_F32
-#define DPA_DGRAD2_SPLIT_F32 4
-#endif
+// The kernels take the split as a template constant S; `split` arguments: 0 = the rule above,
+// 2 / 4 force it (4 on an active site is refused).  DPA_DGRAD2_SPLIT=2 in the environment makes
+// the rule answer 2 for bf16 / fp16 as well (A/B runs); it is read once per process, at the first
+// launch, so a process runs one setting.  fp32 has no knob any more: the epilogue's shapes follow
+// from the split (conv5x5_body ES, 2 or 4), and 4 is its only instantiation.
 template <typename T>
-constexpr int kDgradSplitT = std::is_same<T, float>::value ? DPA_DGRAD2_SPLIT_F32 : DPA_DGRAD2_SPLIT;
-static int dgrad_split(bool fp32) { return fp32 ? DPA_DGRAD2_SPLIT_F32 : DPA_DGRAD2_SPLIT; }
-template <typename T>
-constexpr int kDgrad2WR = conv2_wr<kDgradSplitT<T>, true>();  // whole 2x2 windows: even rows
+constexpr int kDgradSiteSplitT = std::is_same<T, float>::value ? 4 : 2;  // the split of a site launch
+static int dgrad_split(bool fp32, bool site, int64_t split, const char* what) {
+  TORCH_CHECK(split == 0 || split == 2 || split == 4, what, ": split is 0 (by rule), 2 or 4");
+  if (fp32) {
+    TORCH_CHECK(split != 2, what, ": the fp32 data gradient runs 4 workgroups per image");
+    return 4;
+  }
+  TORCH_CHECK(!(site && split == 4), what, ": a launch with an in-kernel exchange site runs 2 workgroups per image");
+  if (split != 0) return (int)split;
+  if (site) return 2;
+  static const bool env2 = [] {
+    const char* e = std::getenv("DPA_DGRAD2_SPLIT");
+    return e != nullptr && std::atoi(e) == 2;
+  }();
+  return env2 ? 2 : 4;
+}
+// runs f(std::integral_constant<int, S>) for the launch's split (fp32 instantiates 4 alone)
+template <typename T, typename F>
+static void with_dgrad_split(int ds, F&& f) {
+  if constexpr (std::is_same<T, float>::value) {
+    f(std::integral_constant<int, 4>{});
+  } else {
+    if (ds == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 4>{});
+  }
+}
+template <int S>
+constexpr int kDgrad2WR = conv2_wr<S, true>();  // whole 2x2 windows: even rows
 // the data-gradient role's kernel body, one spelling for every launch that hosts it
-template <typename T, bool DYN>
+template <typename T, bool DYN, int S>
 __device__ __forceinline__ void conv2_dgrad_role(const T* __restrict__ wpk_d, T* __restrict__ dp1,
                                                  const BwdIn<T>& bi_d, const BwdEpi<T>& ep, int bid) {
-  cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1, DYN, kDgrad2WR<T>>(nullptr, nullptr, nullptr, dp1, nullptr, nullptr,
-                                                                     nullptr, kDgradSplitT<T>, PoolIn<T>{}, bi_d, ep,
-                                                                     wpk_d, cb::WPack<T>{}, bid);
+  cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1, DYN, kDgrad2WR<S>, S>(nullptr, nullptr, nullptr, dp1, nullptr,
+                                                                        nullptr, nullptr, S, PoolIn<T>{}, bi_d, ep,
+                                                                        wpk_d, cb::WPack<T>{}, bid);
 }
-int64_t dgrad2_rows(int64_t B, bool fp32) { return B * dgrad_split(fp32); }
+// rows of bslab1: one per image quarter, whatever the dtype and the split
+int64_t dgrad2_rows(int64_t B, bool fp32) {
+  (void)fp32;
+  return B * cb::EPI_QUARTERS;
+}
+// workgroups of the data-gradient role in a launch with (site) or without an active exchange site
+int64_t dgrad2_wgs(int64_t B, bool fp32, bool site) { return B * dgrad_split(fp32, site, 0, "dgrad2_wgs"); }
 
 // [pool2/ReLU2/BN2 backward] -> conv2 data grad -> dp1 (+ BN1 partial sums rows).
 void conv2_dgrad(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2, at::Tensor fstats2,
                  at::Tensor gsum2, at::Tensor g2, double eps2, at::Tensor dp1, at::Tensor idx1, at::Tensor xh1,
-                 at::Tensor bslab1, XcPtr xc) {
+                 at::Tensor bslab1, XcPtr xc, int64_t split) {
   DPA_CHECK_INPUT(y2); DPA_CHECK_INPUT(dp1); DPA_CHECK_INPUT(wpk_d);
   TORCH_CHECK(wpk_d.numel() == cb::W2D_LEN && wpk_d.scalar_type() == y2.scalar_type(),
               "packed conv2 data-grad weights");
@@ -541,25 +572,28 @@ void conv2_dgrad(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx
   TORCH_CHECK(y2.size(1) == 32 && y2.size(2) == 14 && dp2.numel() == (int64_t)B * 32 * 49);
   TORCH_CHECK(dp1.numel() == (int64_t)B * 16 * 196 && idx1.numel() == dp1.numel() && xh1.numel() == dp1.numel());
   TORCH_CHECK(bslab1.numel() == dgrad2_rows(B, y2.scalar_type() == at::kFloat) * 32, "BN1 partial-sum slab size");
+  const int ds = dgrad_split(y2.scalar_type() == at::kFloat, (bool)xc, split, "conv2_dgrad");
   if (B == 0) return;
   with_t(dt_of(y2), [&](auto tag) {
     typedef decltype(tag) T;
-    constexpr int ds = kDgradSplitT<T>;
-    conv2_row_window(kDgrad2WR<T>, ds, true, "conv2_dgrad");
     BwdIn<T> bi = bwd_in<T>(dp2, idx2, y2, fstats2, gsum2, c10::nullopt, g2, eps2, 32, c10::nullopt, c10::nullopt);
     bi.xs = site_of(xc, xgmi::kSiteBwd2Dgrad);
     xgmi::set_site_grid(bi.xs, B * ds, "conv2_dgrad");
     BwdEpi<T> ep{idx1.data_ptr<uint8_t>(), dptr<T>(xh1), bslab1.data_ptr<float>()};
-    hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<T>>), dim3(B * ds), dim3(cb::NTHR),
-                       0, cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr, nullptr, nullptr,
-                       ds, PoolIn<T>{}, bi, ep, dptr<T>(wpk_d), cb::WPack<T>{});
+    with_dgrad_split<T>(ds, [&](auto sc) {
+      constexpr int S = decltype(sc)::value;
+      conv2_row_window(kDgrad2WR<S>, S, true, "conv2_dgrad");
+      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<S>, S>), dim3(B * S),
+                         dim3(cb::NTHR), 0, cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr, nullptr,
+                         nullptr, S, PoolIn<T>{}, bi, ep, dptr<T>(wpk_d), cb::WPack<T>{});
+    });
   });
   DPA_CHECK_LAUNCH();
 }
 
 // The backward through [BN2 -> ReLU2 -> pool2] feeds two independent products of
-// layer 2: the data grad (-> dp1 + BN1 partial sums, kDgradSplitT<T> workgroups per
-// image) and the weight-grad partials.  One launch hosts both roles -- workgroups
+// layer 2: the data grad (-> dp1 + BN1 partial sums, 2 or 4 workgroups per
+// image: dgrad_split) and the weight-grad partials.  One launch hosts both roles -- workgroups
 // [0, ndg) the data grad, [ndg, grid) the weight grad -- so they overlap on the chip
 // instead of running back to back (each alone fills only 64 / 128 of the 256 CUs at
 // B = 32) and one kernel boundary disappears.
@@ -672,13 +706,13 @@ __device__ __forceinline__ void fc_wgrad_body(const FcW<T>& f, int wg) {
 template <typename T>
 __global__ void __launch_bounds__(cb::NTHR) fc_wgrad_kernel(FcW<T> f) { fc_wgrad_body<T>(f, (int)blockIdx.x); }
 
-template <typename T>
+template <typename T, int S>
 __global__ void __launch_bounds__(cb::NTHR)
 conv2_bwd_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d, BwdEpi<T> ep,
                  const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int ndg, int nwg, FcW<T> fw) {
   const int bid = (int)blockIdx.x;
   if (bid < ndg)
-    conv2_dgrad_role<T, false>(wpk_d, dp1, bi_d, ep, bid);
+    conv2_dgrad_role<T, false, S>(wpk_d, dp1, bi_d, ep, bid);
   else if (bid < ndg + nwg)
     conv2_wgrad_role<T, false>(p1, wslab2, bi_w, bid - ndg);
   else
@@ -691,14 +725,14 @@ conv2_bwd_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d
 // the static arrays, which does not fit a CU's 160 KB -- the reason fp32 ran the data
 // gradient and the weight gradient as two launches, one after the other, each on at
 // most half the CUs (profiles/r6g_cn_steady_fp32.txt: 16.7 + 15.2 us).
-template <typename T>
+template <typename T, int S>
 __global__ void __launch_bounds__(cb::NTHR)
 conv2_bwd_dyn_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d, BwdEpi<T> ep,
                      const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int ndg, int nwg,
                      FcW<T> fw) {
   const int bid = (int)blockIdx.x;
   if (bid < ndg)
-    conv2_dgrad_role<T, true>(wpk_d, dp1, bi_d, ep, bid);
+    conv2_dgrad_role<T, true, S>(wpk_d, dp1, bi_d, ep, bid);
   else if (bid < ndg + nwg)
     conv2_wgrad_role<T, true>(p1, wslab2, bi_w, bid - ndg);
   else
@@ -716,7 +750,7 @@ static bool fp32_merged_bwd() {
     const char* e = std::getenv("DPA_FP32_MERGED_BWD");
     if (e != nullptr && std::atoi(e) == 0) return false;
     const size_t b = conv2_bwd_dyn_bytes<float>();
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<float>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<float, 4>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)b) == hipSuccess;
   }();
   return on;
@@ -731,8 +765,10 @@ static bool lp_dyn_bwd() {
     const char* e = std::getenv("DPA_LP_DYN_BWD");
     if (e != nullptr && std::atoi(e) == 0) return false;
     bool ok = true;
-    for (const void* k : {reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__hip_bfloat16>),
-                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__half>)})
+    for (const void* k : {reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__hip_bfloat16, 2>),
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__hip_bfloat16, 4>),
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__half, 2>),
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__half, 4>)})
       ok = ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)std::max(conv2_bwd_dyn_bytes<__hip_bfloat16>(),
                                                    conv2_bwd_dyn_bytes<__half>())) == hipSuccess;
@@ -810,7 +846,7 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
                at::Tensor bslab1, at::Tensor p1, at::Tensor wslab2, XcPtr xc, c10::optional<at::Tensor> lsum2,
                c10::optional<at::Tensor> dg2, c10::optional<at::Tensor> dbe2, c10::optional<at::Tensor> fc_dls,
                c10::optional<at::Tensor> fc_p2, c10::optional<at::Tensor> fc_dw, c10::optional<at::Tensor> fc_db,
-               c10::optional<at::Tensor> chk) {
+               c10::optional<at::Tensor> chk, int64_t split) {
   DPA_CHECK_INPUT(y2); DPA_CHECK_INPUT(dp1); DPA_CHECK_INPUT(wpk_d); DPA_CHECK_INPUT(p1); DPA_CHECK_INPUT(wslab2);
   TORCH_CHECK(wpk_d.numel() == cb::W2D_LEN && wpk_d.scalar_type() == y2.scalar_type(),
               "packed conv2 data-grad weights");
@@ -822,12 +858,12 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
   TORCH_CHECK(dg2.has_value() == dbe2.has_value(), "conv2_bwd: dg2 and dbe2 go together");
   if (dg2.has_value()) TORCH_CHECK(dg2->numel() == 32 && dbe2->numel() == 32 && dg2->scalar_type() == at::kFloat);
   if (xc) TORCH_CHECK(!lsum2.has_value(), "fused SyncBN exchange: gsum2 must be this rank's rows (no lsum2)");
-  const int ndg = B * dgrad_split(y2.scalar_type() == at::kFloat), nwg = (int)wgrad2_wgs(B);
+  const int ds = dgrad_split(y2.scalar_type() == at::kFloat, (bool)xc, split, "conv2_bwd");
+  const int ndg = B * ds, nwg = (int)wgrad2_wgs(B);
   TORCH_CHECK(wslab2.numel() == wgrad_bn_rows(2, B) * (32 * 400 + 32), "wgrad slab size");
   if (B == 0) return;
   with_t(dt_of(y2), [&](auto tag) {
     typedef decltype(tag) T;
-    conv2_row_window(kDgrad2WR<T>, kDgradSplitT<T>, true, "conv2_bwd data gradient");
     BwdIn<T> bd = bwd_in<T>(dp2, idx2, y2, fstats2, gsum2, lsum2, g2, eps2, 32, dg2, dbe2);
     BwdIn<T> bw = bd;
     bw.dgamma = bw.dbeta = nullptr;  // one writer: the data-gradient role's workgroup 0
@@ -843,24 +879,29 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
       bd.chk = fw.chk = grad_chk_of(chk, xc);
       bd.chk_coef = 1;
     }
-    if (conv2_bwd_dyn<T>()) {  // one launch, the roles' tiles in dynamic LDS (the largest role's bytes)
-      hipLaunchKernelGGL(conv2_bwd_dyn_kernel<T>, dim3(ndg + nwg + nfc), dim3(cb::NTHR), conv2_bwd_dyn_bytes<T>(),
-                         cur_stream(), dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(),
-                         bw, ndg, nwg, fw);
-    } else if constexpr (std::is_same<T, float>::value) {
-      // fp32 static tiles: the two roles' LDS (173 KB) exceed one CU's 160 KB -> separate launches
-      // (the fc weight gradient: extra workgroups of the weight-gradient launch; its site's
-      // tickets are the nwg conv workgroups', set above)
-      bd.xs.nblk = 0;  // the data-gradient launch is its site's whole grid (ndg: checked above)
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<T>>), dim3(ndg), dim3(cb::NTHR), 0,
-                         cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr, nullptr, nullptr,
-                         kDgradSplitT<T>, PoolIn<T>{}, bd, ep, dptr<T>(wpk_d), cb::WPack<T>{});
-      hipLaunchKernelGGL(conv2_wgrad_fc_kernel<T>, dim3(nwg + nfc), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(p1),
-                         wslab2.data_ptr<float>(), bw, nwg, fw);
-    } else {
-      hipLaunchKernelGGL(conv2_bwd_kernel<T>, dim3(ndg + nwg + nfc), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(wpk_d),
-                         dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(), bw, ndg, nwg, fw);
-    }
+    with_dgrad_split<T>(ds, [&](auto sc) {
+      constexpr int S = decltype(sc)::value;
+      conv2_row_window(kDgrad2WR<S>, S, true, "conv2_bwd data gradient");
+      if (conv2_bwd_dyn<T>()) {  // one launch, the roles' tiles in dynamic LDS (the largest role's bytes)
+        hipLaunchKernelGGL((conv2_bwd_dyn_kernel<T, S>), dim3(ndg + nwg + nfc), dim3(cb::NTHR),
+                           conv2_bwd_dyn_bytes<T>(), cur_stream(), dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1),
+                           wslab2.data_ptr<float>(), bw, ndg, nwg, fw);
+      } else if constexpr (std::is_same<T, float>::value) {
+        // fp32 static tiles: the two roles' LDS (173 KB) exceed one CU's 160 KB -> separate launches
+        // (the fc weight gradient: extra workgroups of the weight-gradient launch; its site's
+        // tickets are the nwg conv workgroups', set above)
+        bd.xs.nblk = 0;  // the data-gradient launch is its site's whole grid (ndg: checked above)
+        hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<S>, S>), dim3(ndg),
+                           dim3(cb::NTHR), 0, cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr, nullptr,
+                           nullptr, S, PoolIn<T>{}, bd, ep, dptr<T>(wpk_d), cb::WPack<T>{});
+        hipLaunchKernelGGL(conv2_wgrad_fc_kernel<T>, dim3(nwg + nfc), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(p1),
+                           wslab2.data_ptr<float>(), bw, nwg, fw);
+      } else {
+        hipLaunchKernelGGL((conv2_bwd_kernel<T, S>), dim3(ndg + nwg + nfc), dim3(cb::NTHR), 0, cur_stream(),
+                           dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(), bw, ndg, nwg,
+                           fw);
+      }
+    });
   });
   DPA_CHECK_LAUNCH();
 }
@@ -969,7 +1010,7 @@ bool sites_resident(int64_t B, at::ScalarType st) {
   // every site launch must also fit its site's epoch words (comm/xgmi.h set_site_grid):
   // the conv1 weight gradient's 7 B workgroups pass kEpochWords at B >= 74
   bool ok = xgmi::site_grid_fits(wgrad_bn_rows(1, B)) && xgmi::site_grid_fits(wgrad2_wgs(B)) &&
-            xgmi::site_grid_fits(B * dgrad_split(st == at::kFloat)) &&
+            xgmi::site_grid_fits(dgrad2_wgs(B, st == at::kFloat, true)) &&
             xgmi::site_grid_fits(fwd2_split(st == at::kFloat) * B);
   auto chk = [&](const void* k, int64_t grid) { ok = ok && co_resident(k, (int)grid, cb::NTHR, 0); };
   with_t(dt_of(at::empty({0}, at::TensorOptions().dtype(st))), [&](auto tag) {
@@ -978,13 +1019,13 @@ bool sites_resident(int64_t B, at::ScalarType st) {
         B * fwd2_split(std::is_same<T, float>::value));
     ok = ok && co_resident(reinterpret_cast<const void*>(&head_fwd_kernel<T, 32, 14, 14, 16>), (int)B, HF, 0) &&
          co_resident(reinterpret_cast<const void*>(&head_fwd_kernel<T, 32, 14, 14, 64>), (int)B, HF, 0);
-    chk(reinterpret_cast<const void*>(&cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<T>>), B * kDgradSplitT<T>);
+    constexpr int S = kDgradSiteSplitT<T>;  // what a site launch runs (dgrad_split)
+    chk(reinterpret_cast<const void*>(&cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<S>, S>), B * S);
     if (conv2_bwd_dyn<T>())
-      ok = ok && co_resident(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<T>),
-                             (int)(B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS), cb::NTHR,
-                             conv2_bwd_dyn_bytes<T>());
+      ok = ok && co_resident(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<T, S>),
+                             (int)(B * S + wgrad2_wgs(B) + FC_BLOCKS), cb::NTHR, conv2_bwd_dyn_bytes<T>());
     else if constexpr (!std::is_same<T, float>::value)
-      chk(reinterpret_cast<const void*>(&conv2_bwd_kernel<T>), B * kDgradSplitT<T> + wgrad2_wgs(B) + FC_BLOCKS);
+      chk(reinterpret_cast<const void*>(&conv2_bwd_kernel<T, S>), B * S + wgrad2_wgs(B) + FC_BLOCKS);
     chk(reinterpret_cast<const void*>(&conv2_wgrad_kernel<T>), wgrad2_wgs(B));
     chk(reinterpret_cast<const void*>(&cb::conv5x5_wgrad_kernel<T, 1, 16, 28, 28, WG1_ROWS, 2>),
         wgrad_bn_rows(1, B));
@@ -1003,6 +1044,7 @@ void register_convnet_fused(pybind11::module& m) {
   s.def("head_bwd", &cnf::head_bwd);
   s.def("head_bwd_lds", &cnf::head_bwd_lds);
   s.def("dgrad2_rows", &cnf::dgrad2_rows, py::arg("B"), py::arg("fp32") = false);
+  s.def("dgrad2_wgs", &cnf::dgrad2_wgs, py::arg("B"), py::arg("fp32") = false, py::arg("site") = false);
   // wfc, wfc_pk (trailing, optional): the launch also packs the head's fc weights (cb::pack_fc)
   s.def("conv1_fwd_pack", &cnf::conv1_fwd_pack, py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("y1"),
         py::arg("fslab1"), py::arg("fstats1"), py::arg("shift1"), py::arg("w2"), py::arg("wpk_f"), py::arg("wpk_d"),
@@ -1028,8 +1070,15 @@ void register_convnet_fused(pybind11::module& m) {
 #endif
   s.attr("W2F_LEN") = cb::W2F_LEN;
   s.attr("W2D_LEN") = cb::W2D_LEN;
-  s.def("conv2_dgrad", &cnf::conv2_dgrad);
-  s.def("conv2_bwd", &cnf::conv2_bwd);
+  // split (trailing, optional): data-gradient workgroups per image, 0 = by rule (cnf::dgrad_split)
+  s.def("conv2_dgrad", &cnf::conv2_dgrad, py::arg("wpk_d"), py::arg("y2"), py::arg("dp2"), py::arg("idx2"),
+        py::arg("fstats2"), py::arg("gsum2"), py::arg("g2"), py::arg("eps2"), py::arg("dp1"), py::arg("idx1"),
+        py::arg("xh1"), py::arg("bslab1"), py::arg("xc"), py::arg("split") = 0);
+  s.def("conv2_bwd", &cnf::conv2_bwd, py::arg("wpk_d"), py::arg("y2"), py::arg("dp2"), py::arg("idx2"),
+        py::arg("fstats2"), py::arg("gsum2"), py::arg("g2"), py::arg("eps2"), py::arg("dp1"), py::arg("idx1"),
+        py::arg("xh1"), py::arg("bslab1"), py::arg("p1"), py::arg("wslab2"), py::arg("xc"), py::arg("lsum2"),
+        py::arg("dg2"), py::arg("dbe2"), py::arg("fc_dls"), py::arg("fc_p2"), py::arg("fc_dw"), py::arg("fc_db"),
+        py::arg("chk"), py::arg("split") = 0);
   s.def("fc_wgrad", &cnf::fc_wgrad);
   s.def("conv_wgrad_bn", &cnf::conv_wgrad_bn);
   s.def("wgrad_bn_rows", &cnf::wgrad_bn_rows);

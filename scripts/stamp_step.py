@@ -80,7 +80,9 @@ def wrap(mod, name, roles):
 
 
 B = 32
-NDG = int(C.convnet.dgrad2_rows(B, False))      # data-gradient workgroups (bf16 split count x B)
+# data-gradient workgroups of the bf16 launch: 2 per image with the in-kernel exchange sites
+# (--forced), else 4 (the slab has 4 rows per image either way)
+NDG = int(C.convnet.dgrad2_wgs(B, False, "--forced" in sys.argv))
 NFW = int(C.convnet.fwd2_split(False)) * B      # conv2 forward workgroups
 wrap(C.convnet_head, "head_step", lambda a: [("head_step", slice(0, 32))])
 wrap(C.convnet, "conv2_bwd", lambda a: [("conv2_bwd/dgrad", slice(0, NDG)),
