@@ -76,6 +76,10 @@ def _flags():
     return f
 
 
+# per-file flags: the grouped-conv kernels are built without packed fp32 arithmetic
+_FILE_FLAGS = {"conv_group.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _obj(src: Path) -> Path:
     rel = src.relative_to(CSRC).as_posix().replace("/", "__")
     return BUILD / (rel + ".o")
@@ -93,6 +97,7 @@ def _hash_inputs(src: Path, flags: list[str]) -> str:
 def _compile(src: Path, flags: list[str], force: bool) -> tuple[Path, bool]:
     obj = _obj(src)
     stamp = obj.with_suffix(".sha1")
+    flags = flags + _FILE_FLAGS.get(src.name, [])
     digest = _hash_inputs(src, flags)
     if not force and obj.exists() and stamp.exists() and stamp.read_text() == digest:
         return obj, False

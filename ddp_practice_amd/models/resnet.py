@@ -23,6 +23,10 @@ Execution on a HIP device (``fused=True``): activations are bf16/f16/f32
   * every BatchNorm runs on the native NHWC kernels with its ReLU and, for the
     last BN of a bottleneck, the residual add fused in (ops/bn_nhwc.py), as
     SyncBatchNorm when the module was converted (one small all-reduce each way);
+  * the grouped 3x3 convs of ResNeXt (``groups`` / ``width_per_group``, resnext50_32x4d) run
+    forward, data gradient and weight gradient on the block-diagonal grouped kernels
+    (csrc/kernels/conv_group.hip, ops/conv_group.py; DPA_GCONV=0: library path); the BN
+    that follows takes its own statistics pass;
   * max-pool 3x3/2 and the global average pool are native kernels; fc runs on the
     native MFMA linear kernels (ops/head.py).
 On CPU the plain torch modules run (the same math; the CPU test tier).
@@ -36,6 +40,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..amp import autocast, compute_dtype
+from ..ops import conv_group as _gconv
 from ..ops import conv_igemm as _igemm
 from ..ops.conv1x1 import GradTap, conv1x1
 from ..ops.conv_nhwc import conv_nhwc
@@ -66,6 +71,9 @@ def _conv(x: torch.Tensor, conv: nn.Conv2d, cdtype: torch.dtype, bn: nn.Module |
         if want is None:
             return conv_nhwc(x, conv.weight, conv.stride, conv.padding, cdtype, None, pk, btap), None
         return conv_nhwc(x, conv.weight, conv.stride, conv.padding, cdtype, want, pk, btap)
+    if _gconv.usable(x, conv, cdtype):
+        # grouped 3x3 (ResNeXt) on the block-diagonal MFMA kernels; the BN takes its own statistics
+        return _gconv.conv_group(x, conv.weight, conv.stride[0], conv.groups, cdtype), None
     w = conv.weight.to(cdtype)
     out = F.conv2d(x, w, None if conv.bias is None else conv.bias.to(cdtype), conv.stride, conv.padding,
                    conv.dilation, conv.groups)
@@ -95,12 +103,14 @@ def _comm_of(bn: nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: nn.Module | None = None):
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: nn.Module | None = None,
+                 groups: int = 1, base_width: int = 64):
         super().__init__()
-        width = planes
+        width = int(planes * base_width / 64) * groups  # torchvision's (ResNeXt: groups x base_width)
         self.conv1 = nn.Conv2d(inplanes, width, kernel_size=1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = nn.Conv2d(width, width, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.conv2 = nn.Conv2d(width, width, kernel_size=3, stride=stride, padding=1, groups=groups,
+                               bias=False)
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = nn.Conv2d(width, planes * self.expansion, kernel_size=1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
@@ -163,9 +173,11 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes: int = 1000, amp_dtype: torch.dtype | None = None,
-                 fused: bool = True):
+                 fused: bool = True, groups: int = 1, width_per_group: int = 64):
         super().__init__()
         self.inplanes = 64
+        self.groups = groups
+        self.base_width = width_per_group
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -192,9 +204,10 @@ class ResNet(nn.Module):
                 nn.Conv2d(self.inplanes, planes * Bottleneck.expansion, kernel_size=1, stride=stride, bias=False),
                 nn.BatchNorm2d(planes * Bottleneck.expansion),
             )
-        layers = [Bottleneck(self.inplanes, planes, stride, downsample)]
+        layers = [Bottleneck(self.inplanes, planes, stride, downsample, self.groups, self.base_width)]
         self.inplanes = planes * Bottleneck.expansion
-        layers += [Bottleneck(self.inplanes, planes) for _ in range(1, blocks)]
+        layers += [Bottleneck(self.inplanes, planes, groups=self.groups, base_width=self.base_width)
+                   for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
     # ------------------------------------------------------------------ paths
@@ -261,3 +274,10 @@ class ResNet(nn.Module):
 
 def resnet50(num_classes: int = 1000, amp_dtype: torch.dtype | None = None, fused: bool = True) -> ResNet:
     return ResNet((3, 4, 6, 3), num_classes=num_classes, amp_dtype=amp_dtype, fused=fused)
+
+
+def resnext50_32x4d(num_classes: int = 1000, amp_dtype: torch.dtype | None = None, fused: bool = True) -> ResNet:
+    """ResNeXt-50 32x4d (Xie et al. 2017; torchvision's module tree and state_dict keys,
+    25,028,904 parameters): the 3x3 convs are grouped, 32 groups of 4 / 8 / 16 / 32 channels."""
+    return ResNet((3, 4, 6, 3), num_classes=num_classes, amp_dtype=amp_dtype, fused=fused, groups=32,
+                  width_per_group=4)
