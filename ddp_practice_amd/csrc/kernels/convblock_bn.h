@@ -202,6 +202,20 @@ __device__ __forceinline__ float strided_rowsum(const float* __restrict__ src, i
   return strided_rowsum(src, rows, RL, j, g, G, [] {});
 }
 
+// Sum of column j of a slab whose per-lane-group row sums sit in part[gg * RL + j] (lane
+// tid = g * RL + j wrote slot tid): the G = NTHR / RL groups are added in the order 0 .. G-1,
+// which fixes the bits.  Any lane may ask for any column after the barrier behind the writes:
+// the coefficient lanes add the columns they need themselves, so no second pass through LDS
+// (sums written back, another barrier) stands between the slab loads and the coefficients.
+template <int RL>
+__device__ __forceinline__ float group_colsum(const float* part, int j) {
+  constexpr int G = NTHR / RL;
+  float t = 0.f;
+#pragma unroll
+  for (int gg = 0; gg < G; ++gg) t += part[gg * RL + j];
+  return t;
+}
+
 // part: >= NTHR floats of LDS; ends with __syncthreads().  Every caller runs NTHR-thread
 // workgroups: the constant, not blockDim.x -- on gfx950 blockDim is a load from the hidden
 // kernel arguments, and the s_waitcnt vmcnt(0) before its use waited for every load the
@@ -244,18 +258,28 @@ __device__ __forceinline__ void bn_finalize(const BNParams& bp, float* sc_s, flo
     DPA_STAMP(11);
     __syncthreads();
     DPA_STAMP(12);
-    if (tid < RL) {
-      float t = 0.f;
-      for (int gg = 0; gg < G; ++gg) t += part[gg * RL + tid];
-      part[tid] = t;  // only this thread reads slot tid (its gg = 0 term) before the write
+    float n = 0.f, s1 = 0.f, s2 = 0.f;  // count, sum, sum of squares of channel tid
+    if (xon) {  // (wave-uniform) the exchange wants the local sums as one row in LDS
+      if (tid < RL) {
+        const float t = group_colsum<RL>(part, tid);
+        part[tid] = t;  // only this thread reads slot tid (its gg = 0 term) before the write
+      }
+      __syncthreads();
+      xgmi::xsite_exchange(bp.xs, part, RL, tk, bid);  // local -> global sums (SyncBN)
+      if (tid < C) {
+        n = part[2 * C];
+        s1 = part[tid];
+        s2 = part[C + tid];
+      }
+    } else if (tid < C) {
+      n = group_colsum<RL>(part, 2 * C);
+      s1 = group_colsum<RL>(part, tid);
+      s2 = group_colsum<RL>(part, C + tid);
     }
-    __syncthreads();
-    if (xon) xgmi::xsite_exchange(bp.xs, part, RL, tk, bid);  // local -> global sums (SyncBN)
     if (tid < C) {
-      const float n = part[2 * C];
-      const float m1 = part[tid] / n;
+      const float m1 = s1 / n;
       const float mean = shf + m1;
-      const float var = fmaxf(part[C + tid] / n - m1 * m1, 0.f);
+      const float var = fmaxf(s2 / n - m1 * m1, 0.f);
       const float istd = rsqrtf(var + bp.eps);
       const float s = gam * istd;
       sc_s[tid] = s;
@@ -263,8 +287,8 @@ __device__ __forceinline__ void bn_finalize(const BNParams& bp, float* sc_s, flo
       mean_s[tid] = mean;
       istd_s[tid] = istd;
       if (leader) {
-        bp.fstats[tid] = part[tid];
-        bp.fstats[C + tid] = part[C + tid];
+        bp.fstats[tid] = s1;
+        bp.fstats[C + tid] = s2;
         if (tid == 0) bp.fstats[2 * C] = n;
         const int64_t nb = nb0 + 1;
         const float mom = bp.momentum >= 0.f ? bp.momentum : 1.f / (float)nb;
@@ -352,38 +376,53 @@ struct BwdIn {
   float chk_row_bound = 0.f;
 };
 
-// Column sums of rows x RL floats (row-major) -> out[0..RL) in LDS, using the
-// whole (NTHR-thread) workgroup; part: >= NTHR floats of LDS.  Ends with a barrier.
+// Rows per lane of the BN-backward slab's one load batch (strided_rowsum U) at the step's
+// batch of 32: BN2's slab has one row per image over G = 4 lane groups (8 rows per lane), BN1's
+// one per image quarter (conv5x5.h EPI_QUARTERS) over G = 8 (16 per lane).  RSUM_U loads per
+// lane issued and added 3x / 1.5x what those slabs hold.  Taller slabs take the loop.
+template <int C>
+constexpr int bwd_rsum_u() { return C == 32 ? 8 : C == 16 ? 16 : RSUM_U; }
+
+// Column t of rows x RL floats (row-major) in lane tid = t < RL (0 in the other lanes), using
+// the whole (NTHR-thread) workgroup; part: >= NTHR floats of LDS.  One barrier, between the
+// lanes' row sums and the group adds; part is read after it and not written again.
 // (NTHR, not blockDim.x: see bn_finalize)
-__device__ __forceinline__ void colsum_rows(const float* __restrict__ src, int rows, int RL, float* part,
-                                            float* out) {
-  const int tid = threadIdx.x, nthr = NTHR;
-  const int G = nthr / RL;
+template <int RL, int U, typename F>
+__device__ __forceinline__ float colsum_lane(const float* __restrict__ src, int rows, float* part, F&& after_issue) {
+  const int tid = threadIdx.x;
+  constexpr int G = NTHR / RL;
   const int j = tid % RL, g = tid / RL;
-  part[tid] = g < G ? strided_rowsum(src, rows, RL, j, g, G) : 0.f;
+  if (g < G) {
+    part[tid] = strided_rowsum<U>(src, rows, RL, j, g, G, after_issue);
+  } else {
+    after_issue();
+    part[tid] = 0.f;
+  }
   __syncthreads();
-  float t = 0.f;
-  if (tid < RL)
-    for (int gg = 0; gg < G; ++gg) t += part[gg * RL + tid];
-  __syncthreads();
-  if (tid < RL) out[tid] = t;
-  __syncthreads();
+  return tid < RL ? group_colsum<RL>(part, tid) : 0.f;
 }
 
-// coef (LDS, 5C floats): [k1 | k2 | gi | mean | invstd]; part: >= blockDim.x
-// floats of LDS, sums: >= 2C floats of LDS.  Workgroup `leader` also writes
-// dgamma / dbeta from the local rows.  Ends with a barrier.
-// `part` is scratch of this function alone: its last use is the leader's second colsum_rows, which
-// ends with a barrier.  cb::conv5x5_body's 2-way data-gradient epilogue reuses the same floats for
-// its statistics partials after its compute barrier (conv5x5.h LS_IN_PART), so a caller must not
-// keep anything in `part` past that barrier.
-template <int C, typename T>
+// coef (LDS, 5C floats): [k1 | k2 | gi | mean | invstd]; part: >= NTHR floats of LDS, sums: >= 2C
+// floats of LDS (used with an active exchange site only).  Workgroup `leader` also writes
+// dgamma / dbeta from the local rows.  Two barriers: one inside colsum_lane, one behind the
+// coefficients -- lane t < 2C adds column t's group partials itself and writes k1 / k2 (and, on
+// the leader, dbeta / dgamma) straight from the register.  An active site keeps the sums' round
+// trip through LDS that xsite_exchange needs (two more barriers); the leader of a launch whose
+// local rows differ from the global ones sums those behind the coefficients' barrier.
+// `part` is scratch of this function alone: its last use is the group adds of the last
+// colsum_lane, which no barrier follows.  cb::conv5x5_body's 2-way data-gradient epilogue reuses
+// the same floats for its statistics partials after its compute barrier (conv5x5.h LS_IN_PART):
+// that barrier is what separates the two uses, so a caller must not keep anything in `part` past
+// it, nor write `part` between this function and it.
+template <int C, typename T, int U = bwd_rsum_u<C>()>
 __device__ __forceinline__ void bn_bwd_coef(const BwdIn<T>& bi, float* coef, float* part, float* sums, int bid) {
+  constexpr int RL = 2 * C;
+  static_assert(RL <= NTHR, "one lane per slab column");
   const int tid = threadIdx.x;
   const bool leader = bid == 0;
   float n = 0.f, f0 = 0.f, f1 = 0.f, shf = 0.f, gam = 0.f;
-  if (tid < C) {  // issued before the reduction: latencies overlap
-    n = bi.fstats[2 * C];
+  if (tid < RL) n = bi.fstats[2 * C];  // issued before the reduction: latencies overlap
+  if (tid < C) {
     f0 = bi.fstats[tid];
     f1 = bi.fstats[C + tid];
     shf = bi.fstats[2 * C + 1 + tid];
@@ -393,8 +432,14 @@ __device__ __forceinline__ void bn_bwd_coef(const BwdIn<T>& bi, float* coef, flo
   unsigned long long tk = 0;
   if (xon && tid == 0) tk = xgmi::xsite_ticket(bi.xs, bid);  // latency hides behind the slab loads
   const bool cchk = leader && bi.dgamma != nullptr && bi.chk_coef && !xon;  // producer-side check (xon: above)
-  colsum_rows(bi.gsum, bi.grows, 2 * C, part, sums);
-  if (xon) {
+  // lane t < C: column t = S1 (dbeta) of channel t; lane C + t: S2 (dgamma) of channel t
+  auto put = [&](float v) {
+    if (tid < C) bi.dbeta[tid] = v; else bi.dgamma[tid - C] = v;
+  };
+  float t = colsum_lane<RL, U>(bi.gsum, bi.grows, part, [] {});
+  if (xon) {  // (wave-uniform)
+    if (tid < RL) sums[tid] = t;
+    __syncthreads();
     // dgamma / dbeta are this rank's (DDP averages them); the coefficients use the global sums
     if (leader && bi.dgamma != nullptr && tid < C) {
       bi.dgamma[tid] = sums[C + tid];
@@ -402,31 +447,31 @@ __device__ __forceinline__ void bn_bwd_coef(const BwdIn<T>& bi, float* coef, flo
       if (bi.chk_coef) bi.chk.flag(GradChk::bad(sums[C + tid], bi.chk.bound) || GradChk::bad(sums[tid], bi.chk.bound));
     }
     xgmi::xsite_exchange(bi.xs, sums, 2 * C, tk, bid);
+    if (tid < RL) t = sums[tid];
+  }
+  if (tid < RL) {
+    coef[tid] = t / n;  // k1 | k2
+    if (leader && bi.dgamma != nullptr && bi.lsum == bi.gsum && !xon) {
+      put(t);
+      if (cchk) bi.chk.flag(GradChk::bad(t, bi.chk.bound));
+    }
   }
   if (tid < C) {
     const float m1 = f0 / n;
     const float mean = shf + m1;
     const float istd = rsqrtf(fmaxf(f1 / n - m1 * m1, 0.f) + bi.eps);
-    coef[tid] = sums[tid] / n;
-    coef[C + tid] = sums[C + tid] / n;
     coef[2 * C + tid] = gam * istd;
     coef[3 * C + tid] = mean;
     coef[4 * C + tid] = istd;
-    if (leader && bi.dgamma != nullptr && bi.lsum == bi.gsum && !xon) {
-      bi.dgamma[tid] = sums[C + tid];
-      bi.dbeta[tid] = sums[tid];
-    }
   }
   __syncthreads();
   if (leader && bi.dgamma != nullptr && bi.lsum != bi.gsum && !xon) {
-    colsum_rows(bi.lsum, bi.lrows, 2 * C, part, sums);
-    if (tid < C) {
-      bi.dgamma[tid] = sums[C + tid];
-      bi.dbeta[tid] = sums[tid];
+    const float tl = colsum_lane<RL, RSUM_U>(bi.lsum, bi.lrows, part, [] {});
+    if (tid < RL) {
+      put(tl);
+      if (cchk) bi.chk.flag(GradChk::bad(tl, bi.chk.bound));
     }
   }
-  if (cchk && tid < C)  // the values just written
-    bi.chk.flag(GradChk::bad(sums[C + tid], bi.chk.bound) || GradChk::bad(sums[tid], bi.chk.bound));
 }
 
 // Produce dy[c][h][w] of image b for every 2x2 window.  Two phases so that the
