@@ -51,10 +51,7 @@ import contextlib
 import torch
 
 from .._ext import load as _load_ext
-
-
-def _capturing(dev: torch.device) -> bool:
-    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+from ._device import TableCache
 
 
 class GradAccumulator:
@@ -75,8 +72,7 @@ class GradAccumulator:
         self._acc: dict[int, torch.Tensor] = {}
         self._flat: dict[torch.device, torch.Tensor] = {}
         self._rows = None  # the parameters of the open window
-        self._tables: dict = {}
-        self._tables_pinned: list = []
+        self._tables = TableCache()
         # how a DDP model's average is taken: None (no DDP / one rank), "defer" or "no_sync"
         self._ddp = None
         if steps > 1:
@@ -128,21 +124,10 @@ class GradAccumulator:
             and g.data_ptr() % 4 == 0 for g in grads)
 
     def _table(self, accs, grads):
-        """The device row table of more than MAXT rows, cached per set of gradient pointers and
-        sizes (DDP bucket views keep them fixed; freshly allocated gradients may not).  It is
-        written by launches on the stream (``accum_table``), never from the host, so one built
-        during a graph capture is captured with it; any table a capture looked up stays
-        referenced for the life of the accumulator (as optim/adamw.py ``_table``)."""
+        """The device row table of more than MAXT rows (``_device.TableCache``), keyed on the
+        gradients alone: a parameter's accumulator never moves."""
         key = tuple((g.data_ptr(), g.numel()) for g in grads)
-        t = self._tables.get(key)
-        if t is None:
-            t = _load_ext().accum.accum_table(accs, grads)
-            if len(self._tables) >= 8:
-                self._tables.pop(next(iter(self._tables)))
-            self._tables[key] = t
-        if _capturing(grads[0].device) and not any(x is t for x in self._tables_pinned):
-            self._tables_pinned.append(t)
-        return t
+        return self._tables.get(key, lambda: _load_ext().accum.accum_table(accs, grads), grads[0].device)
 
     @torch.no_grad()
     def accumulate(self, last: bool | None = None) -> bool:

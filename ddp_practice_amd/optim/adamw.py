@@ -35,25 +35,14 @@ disagree on ``step``.
 from __future__ import annotations
 
 import torch
-from torch.optim import Optimizer
 
 from .._ext import load as _load_ext
-from .sgd import _undecorated
+from ._device import DeviceOptimizer, TableCache, _undecorated, capturing, need_eager
 
 
-def _capturing(dev: torch.device) -> bool:
-    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
-
-
-_NEED_EAGER = "{}: the optimizer state must exist before graph capture (run one eager step first)"
-
-
-class Adam(Optimizer):
-    supports_device_found_inf = True
+class Adam(DeviceOptimizer):
     _decoupled = False  # torch.optim.Adam: weight decay added to the gradient
 
-    add_param_group = _undecorated("add_param_group")
-    zero_grad = _undecorated("zero_grad")
     _base_state_dict = _undecorated("state_dict")
     _base_load_state_dict = _undecorated("load_state_dict")
 
@@ -86,9 +75,12 @@ class Adam(Optimizer):
         # any graph capture, as SGD's barrier state is (optim/sgd.py)
         self._tickets: dict[int, torch.Tensor] = {}
         for gi, group in enumerate(self.param_groups):
-            if group["params"] and group["params"][0].is_cuda and not _capturing(group["params"][0].device):
+            if group["params"] and group["params"][0].is_cuda and not capturing(group["params"][0].device):
                 self._ticket(gi, group["params"][0].device)
         self._clip: float | None = None
+        # the update's tables and the norm launch's: two key spaces, one pinned list
+        self._tables = TableCache()
+        self._clip_tables = TableCache(self._tables.pinned)
 
     # ------------------------------------------------------------------ clipping
     def set_grad_clip(self, max_norm: float | None) -> None:
@@ -111,8 +103,7 @@ class Adam(Optimizer):
     def _clip_words(self, dev: torch.device) -> torch.Tensor:
         w = self.__dict__.get("_clip_out")
         if w is None or w.device != dev or w.numel() != 2:
-            if _capturing(dev):
-                raise RuntimeError(_NEED_EAGER.format(type(self).__name__))
+            need_eager(dev, type(self).__name__, "the optimizer state")
             w = self._clip_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
         return w
 
@@ -129,17 +120,14 @@ class Adam(Optimizer):
 
         grads = [g for grp in groups for g in grp[2]]
         out = self._clip_words(grads[0].device)
-        K.grad_norm_into(grads, self._clip, out, grad_scale, found_inf,
-                         self.__dict__.setdefault("_clip_tables", {}), self.__dict__.setdefault("_tables_pinned", []),
-                         type(self).__name__)
+        K.grad_norm_into(grads, self._clip, out, grad_scale, found_inf, self._clip_tables, type(self).__name__)
         return out[1:2]
 
     # ------------------------------------------------------------------ state
     def _ticket(self, gi: int, dev: torch.device) -> torch.Tensor:
         t = self._tickets.get(gi)
         if t is None or t.device != dev:
-            if _capturing(dev):
-                raise RuntimeError(_NEED_EAGER.format(type(self).__name__))
+            need_eager(dev, type(self).__name__, "the optimizer state")
             t = self._tickets[gi] = torch.zeros(1, dtype=torch.int32, device=dev)
         return t
 
@@ -171,8 +159,7 @@ class Adam(Optimizer):
                     raise RuntimeError(f"{type(self).__name__} does not support sparse gradients")
                 st = self.state[p]
                 if not st:
-                    if _capturing(p.device):
-                        raise RuntimeError(_NEED_EAGER.format(type(self).__name__))
+                    need_eager(p.device, type(self).__name__, "the optimizer state")
                     if word is None:
                         word = torch.zeros((), dtype=torch.float32, device=p.device)
                     st["step"] = word
@@ -219,18 +206,6 @@ class Adam(Optimizer):
                 self.state[p]["step"] = word
 
     # ------------------------------------------------------------------ step
-    def _lr_kw(self, gi: int = 0) -> dict:
-        """``lr_dev=`` of group ``gi``'s launch when an ``optim.DeviceLR`` is attached (optim/lr.py)."""
-        w = self.__dict__.get("_lr_words")
-        return {} if w is None else {"lr_dev": w[gi]}
-
-    def _flush_deferred(self):
-        """Average gradients a DDP reducer left to this optimizer (DDP.defer_grad_sync_to hands
-        them to any optimizer with ``fused_amp_step``): every gradient reader calls this first."""
-        d = getattr(self, "_deferred_ddp", None)
-        if d is not None:
-            d[0].flush_deferred()
-
     @staticmethod
     def _native(params, grads, ms, vs) -> bool:
         return params[0].is_cuda and len(params) <= _load_ext().adam.LARGE_MAXT and all(
@@ -238,28 +213,9 @@ class Adam(Optimizer):
             for ts in (params, grads, ms, vs) for t in ts)
 
     def _table(self, gi, params, grads, ms, vs):
-        """Device tensor table of a group of more than MAXT tensors, cached per set of pointers
-        (DDP bucket-view grads and the optimizer state keep them fixed; freshly allocated
-        grads may not).  Any table looked up during graph capture -- built then, or an
-        eager warm-up's table reused from the cache -- stays referenced for the life of
-        the optimizer (the graph reads it on every replay).  The key carries every
-        tensor's size too: memory reused at the same address for a different size must
-        not hit a stale table.  The table is written by launches on the stream
-        (``adam_table``), never from the host: filling the SGD step's table from the host
-        after capture was tried and reverted after a fault in the ResNet bench (README, r5aa)."""
+        """Device tensor table of a group of more than MAXT tensors (``_device.TableCache``)."""
         key = (gi,) + tuple(tuple((t.data_ptr(), t.numel()) for t in ts) for ts in (params, grads, ms, vs))
-        cache = self.__dict__.setdefault("_tables", {})
-        t = cache.get(key)
-        if t is None:
-            t = _load_ext().adam.adam_table(params, grads, ms, vs)
-            if len(cache) >= 8:  # eager tables: the allocator's stream order makes freeing safe
-                cache.pop(next(iter(cache)))
-            cache[key] = t
-        if torch.cuda.is_current_stream_capturing():
-            pinned = self.__dict__.setdefault("_tables_pinned", [])
-            if not any(x is t for x in pinned):
-                pinned.append(t)
-        return t
+        return self._tables.get(key, lambda: _load_ext().adam.adam_table(params, grads, ms, vs), params[0].device)
 
     def _launch_args(self, gi, params, grads, ms, vs):
         """(lists or table) of one group's launches: by value up to MAXT tensors, else the table."""
@@ -301,8 +257,7 @@ class Adam(Optimizer):
             else:
                 if found_inf is not None and bool(found_inf.item()):
                     continue
-                w = self.__dict__.get("_lr_words")
-                self._torch_step(group, params, grads, ms, vs, word, None if w is None else float(w[gi]))
+                self._torch_step(group, params, grads, ms, vs, word, self._host_lr(gi))
         return loss
 
     @staticmethod
@@ -311,7 +266,7 @@ class Adam(Optimizer):
         It advances one count per parameter, so each gets a copy and the word takes the result."""
         from torch.optim import adam as _A
 
-        fn = getattr(_A.adam, "__wrapped__", _A.adam)  # no torch._dynamo import (optim/sgd.py _undecorated)
+        fn = getattr(_A.adam, "__wrapped__", _A.adam)  # no torch._dynamo import (optim/_device.py _undecorated)
         steps = [word.clone() for _ in params]
         b1, b2 = group["betas"]
         fn(params, grads, ms, vs, [], steps, foreach=None, capturable=False, differentiable=False, fused=None,

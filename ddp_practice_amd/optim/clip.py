@@ -22,17 +22,12 @@ from __future__ import annotations
 import torch
 
 from .._ext import load as _load_ext
+from ._device import TableCache, capturing, need_eager
 
-_NEED_EAGER = "{}: its device workspace must exist before graph capture (run one eager step first)"
 _MIN_PARTIALS = 1 << 14  # 64 KiB: 67 M gradient elements before the workspace has to grow
 
 _workspaces: dict[int, dict] = {}
-_tables: dict = {}
-_tables_pinned: list = []
-
-
-def _capturing() -> bool:
-    return torch.cuda.is_current_stream_capturing()
+_tables = TableCache()  # of clip_grad_norm_'s own launches; an optimizer passes its own
 
 
 def chunks_of(grads) -> int:
@@ -46,8 +41,7 @@ def workspace(dev: torch.device, nchunks: int, who: str = "clip_grad_norm_"):
     small stays alive: a captured graph may still write to it."""
     ws = _workspaces.get(dev.index)
     if ws is None or ws["partials"].numel() < nchunks:
-        if _capturing():
-            raise RuntimeError(_NEED_EAGER.format(who))
+        need_eager(dev, who, "its device workspace")
         new = {"partials": torch.empty(max(nchunks, _MIN_PARTIALS), dtype=torch.float32, device=dev),
                "ticket": torch.zeros(1, dtype=torch.int32, device=dev) if ws is None else ws["ticket"],
                "retired": [] if ws is None else ws["retired"] + [ws["partials"]]}
@@ -55,27 +49,14 @@ def workspace(dev: torch.device, nchunks: int, who: str = "clip_grad_norm_"):
     return ws["partials"], ws["ticket"]
 
 
-def grad_table(cache: dict, pinned: list, grads):
-    """The device table of more than MAXT gradients (``adam.adam_table`` with the gradients in
-    every column; the clip kernels read the gradient column), cached per set of pointers and
-    sizes and kept for good once a graph capture has looked it up, as optim/adamw.py ``_table``."""
-    key = tuple((g.data_ptr(), g.numel()) for g in grads)
-    t = cache.get(key)
-    if t is None:
-        t = _load_ext().adam.adam_table(grads, grads, grads, grads)
-        if len(cache) >= 8:
-            cache.pop(next(iter(cache)))
-        cache[key] = t
-    if _capturing() and not any(x is t for x in pinned):
-        pinned.append(t)
-    return t
-
-
-def launch_args(grads, cache: dict | None = None, pinned: list | None = None):
-    """(gradient list, table keywords) of a clip launch: by value up to MAXT tensors, else the table."""
+def launch_args(grads, tables: TableCache = _tables):
+    """(gradient list, table keywords) of a clip launch: by value up to MAXT tensors, else the
+    device table (``adam.adam_table`` with the gradients in every column; the clip kernels read
+    the gradient column)."""
     if len(grads) <= _load_ext().adam.MAXT:
         return grads, {}
-    table = grad_table(_tables if cache is None else cache, _tables_pinned if pinned is None else pinned, grads)
+    key = tuple((g.data_ptr(), g.numel()) for g in grads)
+    table = tables.get(key, lambda: _load_ext().adam.adam_table(grads, grads, grads, grads), grads[0].device)
     return [], {"table": table, "total_granules": sum((g.numel() + 3) // 4 for g in grads)}
 
 
@@ -93,12 +74,12 @@ def native_ok(grads, norm_type=2.0) -> bool:
 
 
 def grad_norm_into(grads, max_norm: float, out: torch.Tensor, grad_scale=None, found_inf=None,
-                   cache: dict | None = None, pinned: list | None = None, who: str = "clip_grad_norm_") -> None:
+                   tables: TableCache = _tables, who: str = "clip_grad_norm_") -> None:
     """The norm launch: ``out[0]`` = the norm of ``grads`` (of ``grads / grad_scale`` with a
     scale word), ``out[1]`` = the clipping coefficient; ``found_inf`` is set, never cleared,
     when a gradient is not finite.  The gradients are only read."""
     partials, ticket = workspace(grads[0].device, chunks_of(grads), who)
-    lst, kw = launch_args(grads, cache, pinned)
+    lst, kw = launch_args(grads, tables)
     _load_ext().clip.grad_norm(lst, float(max_norm), out, partials, ticket, grad_scale, found_inf, **kw)
 
 
@@ -134,7 +115,7 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     grads = [p.grad for p in params if p.grad is not None]
     if not native_ok(grads, norm_type):
         return torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type, error_if_nonfinite, foreach)
-    if error_if_nonfinite and _capturing():
+    if error_if_nonfinite and capturing(grads[0].device):
         raise RuntimeError("clip_grad_norm_(error_if_nonfinite=True) reads the norm on the host, which a graph "
                            "capture cannot do; check optimizer.grad_norm or the returned tensor after the replay")
     partials, _ = workspace(grads[0].device, chunks_of(grads))  # before the allocation below: raises inside a capture

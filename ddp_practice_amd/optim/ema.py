@@ -36,12 +36,7 @@ import contextlib
 import torch
 
 from .._ext import load as _load_ext
-
-_NEED_EAGER = "{}: its device words and row table must exist before graph capture (run one eager update first)"
-
-
-def _capturing(dev: torch.device) -> bool:
-    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+from ._device import TableCache, capturing, need_eager
 
 
 def warmup_weight(n: int, decay: float) -> float:
@@ -80,8 +75,7 @@ class EMA:
         self._one_device = len(devs) == 1
         self._n = torch.zeros((), dtype=torch.int64, device=self.device)
         self._ticket = None
-        self._tables: dict = {}
-        self._tables_pinned: list = []
+        self._tables = TableCache()
 
     # ------------------------------------------------------------------ state
     @property
@@ -100,7 +94,7 @@ class EMA:
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
-        if _capturing(self.device):
+        if capturing(self.device):
             raise RuntimeError("EMA.load_state_dict copies from the host: not under graph capture")
         want = {"n_averaged"} | {"module." + k for k in self.shadows}
         missing, extra = sorted(want - set(sd)), sorted(set(sd) - want)
@@ -150,20 +144,15 @@ class EMA:
         return True
 
     def _table(self, S, X, C):
-        """The device row table of more than MAXT rows, cached per set of pointers and sizes and
-        kept for good once a graph capture has looked it up (as optim/clip.py ``grad_table``)."""
+        """The device row table of more than MAXT rows (``_device.TableCache``); a capture may
+        look one up but not build one."""
         key = tuple((s.data_ptr(), x.data_ptr(), x.numel() * x.element_size(), c) for s, x, c in zip(S, X, C))
-        t = self._tables.get(key)
-        if t is None:
-            if _capturing(self.device):
-                raise RuntimeError(_NEED_EAGER.format("EMA.update"))
-            t = _load_ext().ema.ema_table(S, X, C)
-            if len(self._tables) >= 8:
-                self._tables.pop(next(iter(self._tables)))
-            self._tables[key] = t
-        if _capturing(self.device) and not any(x is t for x in self._tables_pinned):
-            self._tables_pinned.append(t)
-        return t
+
+        def build():
+            need_eager(self.device, "EMA.update", "its device words and row table", "update")
+            return _load_ext().ema.ema_table(S, X, C)
+
+        return self._tables.get(key, build, self.device)
 
     @torch.no_grad()
     def update(self) -> None:
@@ -173,8 +162,7 @@ class EMA:
             return self._fallback(S, X, C)
         E = _load_ext().ema
         if self._ticket is None:
-            if _capturing(self.device):
-                raise RuntimeError(_NEED_EAGER.format("EMA.update"))
+            need_eager(self.device, "EMA.update", "its device words and row table", "update")
             self._ticket = torch.zeros(1, dtype=torch.int32, device=self.device)
         kw = {}
         lists = (S, X, C)
@@ -186,7 +174,7 @@ class EMA:
         E.ema_update(*lists, self._n, self._ticket, 1.0 - self.decay, self.decay, self.warmup, **kw)
 
     def _fallback(self, S, X, C) -> None:
-        if _capturing(self.device):
+        if capturing(self.device):
             raise RuntimeError("EMA.update: this set of tensors takes the torch fallback, which reads n_averaged "
                                "on the host and cannot be captured")
         n = int(self._n)
@@ -214,7 +202,7 @@ class EMA:
     def applied(self):
         """Run the body with the averaged weights in the model's own tensors; the live values
         are copied back on exit, bit for bit.  Eager only."""
-        if _capturing(self.device):
+        if capturing(self.device):
             raise RuntimeError("EMA.applied copies whole models: not under graph capture")
         with torch.no_grad():
             live = {k: v.detach().clone() for k, v in self._sources.items()}

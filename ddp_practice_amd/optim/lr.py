@@ -21,10 +21,7 @@ from typing import Callable, Sequence
 import torch
 
 from .._ext import load as _load_ext
-
-
-def _capturing(dev: torch.device) -> bool:
-    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+from ._device import capturing
 
 
 class DeviceLR:
@@ -52,7 +49,7 @@ class DeviceLR:
         if len(devs) != 1:
             raise ValueError("DeviceLR: the optimizer's parameters must be on one device")
         self.device = devs.pop()
-        if _capturing(self.device):
+        if capturing(self.device):
             raise RuntimeError("DeviceLR: create the schedule outside graph capture")
         self.optimizer = optimizer
         # float32 of the Python double: what torch's foreach SGD rounds its lr to
@@ -92,7 +89,7 @@ class DeviceLR:
 
     # -- host-syncing methods: each reads from or writes to the device, none under capture
     def _no_capture(self, what: str) -> None:
-        if _capturing(self.device):
+        if capturing(self.device):
             raise RuntimeError(f"DeviceLR.{what} synchronises with the host: not under graph capture")
 
     def get_last_lr(self) -> list[float]:

@@ -12,20 +12,9 @@ from __future__ import annotations
 import os
 
 import torch
-from torch.optim import Optimizer
 
 from .._ext import load as _load_ext
-
-
-def _undecorated(name):
-    """``torch.optim.Optimizer.<name>`` without its ``torch._disable_dynamo`` wrapper.
-
-    The wrapper imports ``torch._dynamo`` on first use (~1.2 s, measured: the largest
-    single cost of a 3-epoch CLI run); this framework never traces an optimizer, so the
-    plain function is called.
-    """
-    fn = getattr(Optimizer, name)
-    return getattr(fn, "__wrapped__", fn)
+from ._device import DeviceOptimizer, TableCache, _undecorated, capturing, need_eager
 
 
 # the plain step on the fused launch (slab sums and the deferred DDP average inside it);
@@ -33,14 +22,11 @@ def _undecorated(name):
 _PLAIN_FUSED = os.environ.get("DPA_PLAIN_FUSED", "1") != "0"
 
 
-class SGD(Optimizer):
-    supports_device_found_inf = True
+class SGD(DeviceOptimizer):
     # step() without a GradScaler runs the fused launch when _fuse_kind() is "small", so
     # the engine may hand it the deferred slab / DDP average (engine.TrainLoop)
     plain_fused = _PLAIN_FUSED
 
-    add_param_group = _undecorated("add_param_group")
-    zero_grad = _undecorated("zero_grad")
     state_dict = _undecorated("state_dict")
     load_state_dict = _undecorated("load_state_dict")
 
@@ -57,6 +43,7 @@ class SGD(Optimizer):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                         nesterov=nesterov, maximize=maximize)
         super().__init__(params, defaults)
+        self._tables = TableCache()  # of the large fused step
         # grid-barrier state of the fused AMP step, zeroed here, outside any graph capture:
         # created lazily inside a capture, its zero-fill became a graph node that re-ran on
         # every replay (profiles/r4final_convnet_steady.txt)
@@ -79,7 +66,7 @@ class SGD(Optimizer):
         outside a graph capture only; None inside one when they do not exist yet."""
         t = self.__dict__.get("_grad_chk")
         if t is None or t.numel() != n or t.device != device:
-            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            if capturing(device):
                 return None
             t = self._grad_chk = torch.empty(n, dtype=torch.int32, device=device)
         return t
@@ -99,19 +86,10 @@ class SGD(Optimizer):
         if ps is not None:
             _load_ext().convblock.slab_reduce(ps[0], ps[1].numel(), ps[1])
 
-    def _lr_kw(self, gi: int = 0) -> dict:
-        """``lr_dev=`` of group ``gi``'s update launch: its device-resident rate when an
-        ``optim.DeviceLR`` is attached (optim/lr.py), else nothing -- the call is today's."""
-        w = self.__dict__.get("_lr_words")
-        return {} if w is None else {"lr_dev": w[gi]}
-
     def _flush_deferred(self):
-        """Average gradients a DDP reducer left to this optimizer (DDP.defer_grad_sync_to)
-        and sum a deferred gradient slab (defer_slab)."""
+        """Sum a deferred gradient slab (defer_slab), then the DDP average."""
         self.flush_slab()
-        d = getattr(self, "_deferred_ddp", None)
-        if d is not None:
-            d[0].flush_deferred()
+        super()._flush_deferred()
 
     @torch.no_grad()
     def step(self, closure=None, found_inf: torch.Tensor | None = None):
@@ -136,8 +114,7 @@ class SGD(Optimizer):
             else:
                 if found_inf is not None and bool(found_inf.item()):
                     continue
-                w = self.__dict__.get("_lr_words")
-                self._torch_step(group, params, grads, bufs, first, None if w is None else float(w[gi]))
+                self._torch_step(group, params, grads, bufs, first, self._host_lr(gi))
         return loss
 
     # ------------------------------------------------------------------ AMP
@@ -204,27 +181,11 @@ class SGD(Optimizer):
         return self._fuse_kind() is not None
 
     def _large_table(self, params, grads, bufs, first):
-        """Device tensor table of the large fused step, cached per set of pointers (DDP
-        bucket-view grads and the optimizer state keep them fixed; freshly allocated
-        grads may not).  Any table looked up during graph capture -- built then, or an
-        eager warm-up's table reused from the cache -- stays referenced for the life of
-        the optimizer (the graph reads it on every replay).  The key carries every
-        tensor's size too: memory reused at the same address for a different size must
-        not hit a stale table."""
+        """Device tensor table of the large fused step (``_device.TableCache``)."""
         key = (tuple((p.data_ptr(), p.numel()) for p in params), tuple((g.data_ptr(), g.numel()) for g in grads),
                tuple((b.data_ptr(), b.numel()) for b in bufs), tuple(first))
-        cache = self.__dict__.setdefault("_amp_tables", {})
-        t = cache.get(key)
-        if t is None:
-            t = _load_ext().optim.amp_sgd_table(params, grads, bufs, first)
-            if len(cache) >= 8:  # eager tables: the allocator's stream order makes freeing safe
-                cache.pop(next(iter(cache)))
-            cache[key] = t
-        if torch.cuda.is_current_stream_capturing():
-            pinned = self.__dict__.setdefault("_amp_tables_pinned", [])
-            if not any(x is t for x in pinned):
-                pinned.append(t)
-        return t
+        return self._tables.get(key, lambda: _load_ext().optim.amp_sgd_table(params, grads, bufs, first),
+                                params[0].device)
 
     @torch.no_grad()
     def fused_amp_step(self, scale, tracker, found_inf, growth, backoff, interval):
@@ -235,9 +196,7 @@ class SGD(Optimizer):
         if sync is None or sync.device != params[0].device:
             # grid-barrier state of the fused kernel (allocated before any graph capture:
             # the first step runs eagerly)
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("SGD: the fused AMP step's barrier state must exist before graph capture "
-                                   "(run one eager step first)")
+            need_eager(params[0].device, "SGD", "the fused AMP step's barrier state")
             sync = torch.zeros(4, dtype=torch.int64, device=params[0].device)
             setattr(self, name, sync)
         O = _load_ext().optim
@@ -277,9 +236,7 @@ class SGD(Optimizer):
         (group, params, grads, bufs, first), = self._collect()
         sync = getattr(self, "_amp_sync", None)
         if sync is None or sync.device != params[0].device:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("SGD: the fused step's state must exist before graph capture "
-                                   "(run one eager step first)")
+            need_eager(params[0].device, "SGD", "the fused step's state")
             sync = self._amp_sync = torch.zeros(4, dtype=torch.int64, device=params[0].device)
         d = getattr(self, "_deferred_ddp", None)
         xc = d[1] if d is not None and d[0].deferred_pending() else None

@@ -305,7 +305,7 @@ def test_captured_window_replayed_equals_eager(C, opt_name, count):
         window(mb, ob, ab)
     assert ab._flat[DEV] is flat and ab.position == 0
     if count > C.accum.MAXT:
-        assert len(ab._tables_pinned) >= 1
+        assert len(ab._tables.pinned) >= 1
     _exact([p.detach() for p in mb.ps], snap, "capture runs nothing")
     for _ in range(4):
         graph.replay()

@@ -314,6 +314,87 @@ def test_state_must_exist_before_capture(C):
     assert float(opt.state[p]["step"]) == 1.0
 
 
+def _table_caches(opt, acc):
+    """(tables by key, pinned tables) of every table cache an update of ``opt`` (through ``acc``) uses."""
+    return [(c.tables, c.pinned) for c in [opt._tables] + ([acc._tables] if acc is not None else [])]
+
+
+@pytest.mark.parametrize("accum", [False, True], ids=["AdamW", "GradAccumulator-AdamW"])
+def test_replay_after_the_captured_table_was_evicted(C, accum):
+    """A captured update keeps reading its device tables after eight eager updates on freshly
+    allocated gradients have turned the 8-entry cache over: the replays equal an all-eager twin
+    bit for bit, the captured tables are still pinned and their keys are gone from the cache.
+    37 parameters of 5, 4 and 1031 elements (a tail granule, an exact one, several chunks): the
+    smallest set that takes the table route."""
+    from ddp_practice_amd.optim import AdamW, GradAccumulator
+
+    micro = 2 if accum else 1  # gradient sets per update
+    sizes = [(5, 4, 1031)[i % 3] for i in range(C.adam.MAXT + 1)]
+    assert len(sizes) > C.accum.MAXT
+    gen = torch.Generator().manual_seed(17)
+    init = [torch.randn(n, generator=gen) for n in sizes]
+    vals = [[[_grad(n, gen) for n in sizes] for _ in range(micro)] for _ in range(9)]  # vals[0]: the static set
+
+    def make():
+        ps = [torch.nn.Parameter(p.to(DEV)) for p in init]
+        opt = AdamW(ps, lr=1e-2, weight_decay=0.01)
+        return ps, opt, (GradAccumulator(opt, steps=2) if accum else None)
+
+    def fresh(u):
+        return [[g.to(DEV) for g in gs] for gs in vals[u]]
+
+    def update(ps, opt, acc, sets):
+        for gs in sets:
+            for p, g in zip(ps, gs):
+                p.grad = g
+            done = acc.accumulate() if acc is not None else True
+        assert done
+        opt.step()
+
+    def outputs(ps, opt):
+        return [p.detach() for p in ps] + sum(_state(opt, ps), []) + [opt.state[ps[0]]["step"].reshape(1)]
+
+    pa, oa, aa = make()
+    for u in [0] + list(range(1, 9)) + [0, 0]:
+        update(pa, oa, aa, fresh(u))
+
+    pb, ob, ab = make()
+    static = fresh(0)
+    update(pb, ob, ab, static)  # 1. eager: the state and the tables exist
+    snap = [x.clone() for x in outputs(pb, ob)]
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):  # 2. the capture looks the eager tables up
+        update(pb, ob, ab, static)
+    caches = _table_caches(ob, ab)
+    captured = [dict(tables) for tables, _ in caches]
+    assert [len(c) for c in captured] == ([1, 2] if accum else [1])
+    for (_, pinned), cap in zip(caches, captured):
+        assert all(any(x is t for x in pinned) for t in cap.values())
+    _exact(outputs(pb, ob), snap, "capture runs nothing")
+    with torch.no_grad():
+        for x, s in zip(outputs(pb, ob), snap):
+            x.copy_(s)
+    keep = [static]  # the old gradients stay alive: every update below has pointers of its own
+    for u in range(1, 9):  # 3. eight new keys per cache
+        keep.append(fresh(u))
+        update(pb, ob, ab, keep[-1])
+    for (tables, pinned), cap in zip(caches, captured):
+        for key, t in cap.items():
+            assert key not in tables and len(tables) == 8
+            assert any(x is t for x in pinned)
+    for _ in range(2):
+        for ss, vs in zip(static, vals[0]):  # 4. the window's last set was overwritten with its mean
+            for s, v in zip(ss, vs):
+                s.copy_(v)
+        for p, g in zip(pb, static[-1]):
+            p.grad = g
+        graph.replay()  # 5.
+    torch.cuda.synchronize()
+    _exact(outputs(pb, ob), outputs(pa, oa), "replays after eviction vs the all-eager twin")
+    assert float(ob.state[pb[0]]["step"]) == 11.0
+    del graph
+
+
 # ---------------------------------------------------------------- 5. DeviceLR
 def test_device_lr_eager_equals_replay_and_follows_torch_scheduler(C):
     from ddp_practice_amd.optim import AdamW, DeviceLR

@@ -558,15 +558,15 @@ def test_large_table_pinned_when_reused_under_capture(C):
         p.grad = torch.randn_like(p)
     params, grads = list(ps), [p.grad for p in ps]
     t_eager = opt._large_table(params, grads, [], [])
-    assert not opt.__dict__.get("_amp_tables_pinned")
+    assert not opt._tables.pinned
     s = torch.cuda.Stream()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.stream(s):
         with torch.cuda.graph(g):
             t_cap = opt._large_table(params, grads, [], [])
     assert t_cap is t_eager
-    assert any(x is t_eager for x in opt._amp_tables_pinned)
-    key = next(iter(opt._amp_tables))
+    assert any(x is t_eager for x in opt._tables.pinned)
+    key = next(iter(opt._tables.tables))
     assert key[0][0] == (ps[0].data_ptr(), ps[0].numel())
 
 
