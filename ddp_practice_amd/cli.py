@@ -19,12 +19,14 @@ Additive flags (all optional; defaults reproduce the reference):
                                       autocast, GradScaler, SGD, SyncBatchNorm and DDP
                                       (parity / same-node baseline runs)
   --seed N                            model-init seed
-  --model {convnet,resnet50,resnext50_32x4d}
+  --model {convnet,resnet50,resnext50_32x4d,se_resnet50,se_resnext50_32x4d}
                                       resnet50 = BASELINE.json config 5 (ResNet-50, torchvision
                                       layout) on a synthetic ImageNet-shaped set
                                       (--image-size, --num-classes; data/imagenet.py);
                                       resnext50_32x4d = ResNeXt-50 32x4d on the same set (its
-                                      grouped 3x3 convs on ops/conv_group.py)
+                                      grouped 3x3 convs on ops/conv_group.py);
+                                      se_resnet50 / se_resnext50_32x4d = the two with a
+                                      squeeze-and-excitation gate per block (ops/se.py)
   --lr / --momentum / --weight-decay  SGD hyper-parameters (defaults: the reference's SGD(params, 1e-4))
   --optimizer {sgd,adamw,adam}        adamw / adam: optim.AdamW / optim.Adam, one native launch per step whose
                                       step count lives on the device, so it replays from the step graph
@@ -90,9 +92,11 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
     parser.add_argument("--metrics-file", default=None, help="per-epoch JSONL metrics (rank 0)")
     parser.add_argument("--impl", default="native", choices=["native", "torch"],
                         help="torch: run the same program on PyTorch's own stack (parity / baseline)")
-    parser.add_argument("--model", default="convnet", choices=["convnet", "resnet50", "resnext50_32x4d"],
+    parser.add_argument("--model", default="convnet",
+                        choices=["convnet", "resnet50", "resnext50_32x4d", "se_resnet50", "se_resnext50_32x4d"],
                         help="resnet50: ResNet-50 on synthetic 3 x S x S images (BASELINE.json config 5); "
-                             "resnext50_32x4d: ResNeXt-50 32x4d on the same images")
+                             "resnext50_32x4d: ResNeXt-50 32x4d on the same images; "
+                             "se_resnet50 / se_resnext50_32x4d: the two with squeeze-and-excitation gates")
     parser.add_argument("--lr", type=float, default=1e-4, help="SGD learning rate (the schedule's base rate)")
     parser.add_argument("--momentum", type=float, default=0.0)
     parser.add_argument("--weight-decay", type=float, default=0.0)
@@ -384,7 +388,8 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     ds_box: dict = {}
 
     # an ImageNet-shaped model: the synthetic image set, --image-size / --num-classes, one step per graph
-    resnet = getattr(args, "model", "convnet") in ("resnet50", "resnext50_32x4d")
+    resnet = getattr(args, "model", "convnet") in ("resnet50", "resnext50_32x4d", "se_resnet50",
+                                                   "se_resnext50_32x4d")
     from ddp_practice_amd.data.mnist import idx_available
 
     on_device = (not resnet and torch.cuda.is_available()

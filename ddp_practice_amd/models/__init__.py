@@ -1,3 +1,4 @@
-"""Model zoo: the reference ConvNet, the ResNet-50 stress config and ResNeXt-50 32x4d."""
+"""Model zoo: the reference ConvNet, the ResNet-50 stress config, ResNeXt-50 32x4d and their
+squeeze-and-excitation variants."""
 from .convnet import ConvNet  # noqa: F401
-from .resnet import ResNet, resnet50, resnext50_32x4d  # noqa: F401
+from .resnet import ResNet, resnet50, resnext50_32x4d, se_resnet50, se_resnext50_32x4d  # noqa: F401

@@ -27,6 +27,13 @@ Execution on a HIP device (``fused=True``): activations are bf16/f16/f32
     forward, data gradient and weight gradient on the block-diagonal grouped kernels
     (csrc/kernels/conv_group.hip, ops/conv_group.py; DPA_GCONV=0: library path); the BN
     that follows takes its own statistics pass;
+  * squeeze-and-excitation (``se_reduction``; se_resnet50, se_resnext50_32x4d: Hu et al. 2018,
+    timm's ``layerL.B.se.fc{1,2}`` keys): bn3 is applied without ReLU or residual, and the
+    pool, the two fp32 gate layers (fp32 MFMA), the sigmoid, the channel scale, the residual add
+    and the ReLU run in three launches forward and four backward (csrc/kernels/se.hip,
+    ops/se.py; DPA_SE=0: a torch composition of the same math on the same convs).  An identity
+    block's d(identity) still goes to conv1's data gradient through the GradTap; the block
+    output is not a BN's, so the next block's conv1 takes no BNTap sums;
   * max-pool 3x3/2 and the global average pool are native kernels; fc runs on the
     native MFMA linear kernels (ops/head.py).
 On CPU the plain torch modules run (the same math; the CPU test tier).
@@ -42,6 +49,7 @@ import torch.nn.functional as F
 from ..amp import autocast, compute_dtype
 from ..ops import conv_group as _gconv
 from ..ops import conv_igemm as _igemm
+from ..ops import se as _se
 from ..ops.conv1x1 import GradTap, conv1x1
 from ..ops.conv_nhwc import conv_nhwc
 
@@ -100,11 +108,24 @@ def _comm_of(bn: nn.Module):
     return bn_comm(bn)
 
 
+class SqueezeExcite(nn.Module):
+    """x * sigmoid(fc2(relu(fc1(mean_hw x)))): two 1x1 convs with bias on the pooled vector."""
+
+    def __init__(self, channels: int, reduction: int):
+        super().__init__()
+        self.fc1 = nn.Conv2d(channels, channels // reduction, kernel_size=1)
+        self.fc2 = nn.Conv2d(channels // reduction, channels, kernel_size=1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        s = F.relu(self.fc1(x.mean((2, 3), keepdim=True)))
+        return x * torch.sigmoid(self.fc2(s))
+
+
 class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: nn.Module | None = None,
-                 groups: int = 1, base_width: int = 64):
+                 groups: int = 1, base_width: int = 64, se_reduction: int = 0):
         super().__init__()
         width = int(planes * base_width / 64) * groups  # torchvision's (ResNeXt: groups x base_width)
         self.conv1 = nn.Conv2d(inplanes, width, kernel_size=1, bias=False)
@@ -115,6 +136,8 @@ class Bottleneck(nn.Module):
         self.conv3 = nn.Conv2d(width, planes * self.expansion, kernel_size=1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
         self.relu = nn.ReLU(inplace=True)
+        if se_reduction:
+            self.se = SqueezeExcite(planes * self.expansion, se_reduction)
         self.downsample = downsample
         self.stride = stride
 
@@ -123,6 +146,8 @@ class Bottleneck(nn.Module):
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
+        if hasattr(self, "se"):
+            out = self.se(out)
         if self.downsample is not None:
             identity = self.downsample(x)
         return self.relu(out + identity)
@@ -143,7 +168,8 @@ class Bottleneck(nn.Module):
         # (ops/bn_nhwc.BNTap): bn2 -> conv3, and the previous block's bn3 -> this conv1
         # when this is an identity block (its dgrad then holds the whole gradient of x);
         # bn1 -> conv2 (stride 1) with DPA_FUSE_BN1=1
-        bt_in = bt_in if tap is not None else None
+        se = getattr(self, "se", None)
+        bt_in = bt_in if (tap is not None and se is None) else None  # (an SE block's x is no BN's output)
         bt1 = BNTap() if train and _FUSE_BN1 and self.conv2.stride == (1, 1) else None
         bt2 = BNTap() if train and _FUSE_BN_BWD else None
         bt3 = BNTap() if train and _FUSE_BN_BWD else None
@@ -157,9 +183,16 @@ class Bottleneck(nn.Module):
         if self.downsample is not None:
             conv, bn = self.downsample[0], self.downsample[1]
             cd, std = _conv(x, conv, cdtype, bn, None, xtap)
-            if not _FUSE_DS_BN:
+            if not _FUSE_DS_BN or se is not None:
                 identity = bn_act(cd, bn, relu=False, comm=_comm_of(bn), stats=std)
         c3, st = _conv(out, self.conv3, cdtype, self.bn3, btap=bt2)
+        if se is not None:
+            # bn3 without ReLU or residual; the gate, the residual add and the ReLU on the SE kernels
+            u = bn_act(c3, self.bn3, relu=False, comm=_comm_of(self.bn3), stats=st)
+            gate = (se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias)
+            if _se.usable(u, se.fc1.in_channels, se.fc1.out_channels, cdtype):
+                return _se.squeeze_excite(u, identity, *gate, tap=tap), None
+            return _se.squeeze_excite_torch(u, identity, *gate), None
         if cd is not None and _FUSE_DS_BN:
             # downsample BN applied inside the residual add (no normalised identity written)
             from ..ops.bn_nhwc import bn_res_bn
@@ -173,10 +206,11 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, layers=(3, 4, 6, 3), num_classes: int = 1000, amp_dtype: torch.dtype | None = None,
-                 fused: bool = True, groups: int = 1, width_per_group: int = 64):
+                 fused: bool = True, groups: int = 1, width_per_group: int = 64, se_reduction: int = 0):
         super().__init__()
         self.inplanes = 64
         self.groups = groups
+        self.se_reduction = se_reduction
         self.base_width = width_per_group
         self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -204,10 +238,11 @@ class ResNet(nn.Module):
                 nn.Conv2d(self.inplanes, planes * Bottleneck.expansion, kernel_size=1, stride=stride, bias=False),
                 nn.BatchNorm2d(planes * Bottleneck.expansion),
             )
-        layers = [Bottleneck(self.inplanes, planes, stride, downsample, self.groups, self.base_width)]
+        layers = [Bottleneck(self.inplanes, planes, stride, downsample, self.groups, self.base_width,
+                             self.se_reduction)]
         self.inplanes = planes * Bottleneck.expansion
-        layers += [Bottleneck(self.inplanes, planes, groups=self.groups, base_width=self.base_width)
-                   for _ in range(1, blocks)]
+        layers += [Bottleneck(self.inplanes, planes, groups=self.groups, base_width=self.base_width,
+                              se_reduction=self.se_reduction) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
     # ------------------------------------------------------------------ paths
@@ -281,3 +316,15 @@ def resnext50_32x4d(num_classes: int = 1000, amp_dtype: torch.dtype | None = Non
     25,028,904 parameters): the 3x3 convs are grouped, 32 groups of 4 / 8 / 16 / 32 channels."""
     return ResNet((3, 4, 6, 3), num_classes=num_classes, amp_dtype=amp_dtype, fused=fused, groups=32,
                   width_per_group=4)
+
+
+def se_resnet50(num_classes: int = 1000, amp_dtype: torch.dtype | None = None, fused: bool = True) -> ResNet:
+    """SE-ResNet-50 (Hu et al. 2018; 28,088,024 parameters): ResNet-50 with a squeeze-and-excitation
+    gate of reduction 16 after every bn3, under timm's ``se.fc1`` / ``se.fc2`` keys."""
+    return ResNet((3, 4, 6, 3), num_classes=num_classes, amp_dtype=amp_dtype, fused=fused, se_reduction=16)
+
+
+def se_resnext50_32x4d(num_classes: int = 1000, amp_dtype: torch.dtype | None = None, fused: bool = True) -> ResNet:
+    """SE-ResNeXt-50 32x4d (27,559,896 parameters): resnext50_32x4d with the same SE gates."""
+    return ResNet((3, 4, 6, 3), num_classes=num_classes, amp_dtype=amp_dtype, fused=fused, groups=32,
+                  width_per_group=4, se_reduction=16)
