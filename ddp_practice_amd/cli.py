@@ -19,14 +19,16 @@ Additive flags (all optional; defaults reproduce the reference):
                                       autocast, GradScaler, SGD, SyncBatchNorm and DDP
                                       (parity / same-node baseline runs)
   --seed N                            model-init seed
-  --model {convnet,resnet50,resnext50_32x4d,se_resnet50,se_resnext50_32x4d}
+  --model {convnet,resnet50,resnext50_32x4d,se_resnet50,se_resnext50_32x4d,mobilenet_v1}
                                       resnet50 = BASELINE.json config 5 (ResNet-50, torchvision
                                       layout) on a synthetic ImageNet-shaped set
                                       (--image-size, --num-classes; data/imagenet.py);
                                       resnext50_32x4d = ResNeXt-50 32x4d on the same set (its
                                       grouped 3x3 convs on ops/conv_group.py);
                                       se_resnet50 / se_resnext50_32x4d = the two with a
-                                      squeeze-and-excitation gate per block (ops/se.py)
+                                      squeeze-and-excitation gate per block (ops/se.py);
+                                      mobilenet_v1 = MobileNetV1 on the same set (its depthwise
+                                      3x3 convs on ops/conv_dw.py)
   --lr / --momentum / --weight-decay  SGD hyper-parameters (defaults: the reference's SGD(params, 1e-4))
   --optimizer {sgd,adamw,adam}        adamw / adam: optim.AdamW / optim.Adam, one native launch per step whose
                                       step count lives on the device, so it replays from the step graph
@@ -93,10 +95,12 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
     parser.add_argument("--impl", default="native", choices=["native", "torch"],
                         help="torch: run the same program on PyTorch's own stack (parity / baseline)")
     parser.add_argument("--model", default="convnet",
-                        choices=["convnet", "resnet50", "resnext50_32x4d", "se_resnet50", "se_resnext50_32x4d"],
+                        choices=["convnet", "resnet50", "resnext50_32x4d", "se_resnet50", "se_resnext50_32x4d",
+                                 "mobilenet_v1"],
                         help="resnet50: ResNet-50 on synthetic 3 x S x S images (BASELINE.json config 5); "
                              "resnext50_32x4d: ResNeXt-50 32x4d on the same images; "
-                             "se_resnet50 / se_resnext50_32x4d: the two with squeeze-and-excitation gates")
+                             "se_resnet50 / se_resnext50_32x4d: the two with squeeze-and-excitation gates; "
+                             "mobilenet_v1: MobileNetV1 (depthwise-separable) on the same images")
     parser.add_argument("--lr", type=float, default=1e-4, help="SGD learning rate (the schedule's base rate)")
     parser.add_argument("--momentum", type=float, default=0.0)
     parser.add_argument("--weight-decay", type=float, default=0.0)
@@ -117,8 +121,8 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
                         help="update n uses min(decay, (1 + n) / (10 + n)); native route only")
     parser.add_argument("--accum-steps", type=int, default=1,
                         help="micro-batches per optimizer update (gradient accumulation; default 1)")
-    parser.add_argument("--image-size", type=int, default=224, help="resnet50 / resnext50_32x4d: synthetic image side")
-    parser.add_argument("--num-classes", type=int, default=1000, help="resnet50 / resnext50_32x4d: synthetic label count")
+    parser.add_argument("--image-size", type=int, default=224, help="resnet50 / resnext50_32x4d / mobilenet_v1: synthetic image side")
+    parser.add_argument("--num-classes", type=int, default=1000, help="resnet50 / resnext50_32x4d / mobilenet_v1: synthetic label count")
     if distributed:
         parser.add_argument("--no-sync-bn", action="store_true")
         parser.add_argument("--bucket-cap-mb", type=float, default=None)
@@ -389,7 +393,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
 
     # an ImageNet-shaped model: the synthetic image set, --image-size / --num-classes, one step per graph
     resnet = getattr(args, "model", "convnet") in ("resnet50", "resnext50_32x4d", "se_resnet50",
-                                                   "se_resnext50_32x4d")
+                                                   "se_resnext50_32x4d", "mobilenet_v1")
     from ddp_practice_amd.data.mnist import idx_available
 
     on_device = (not resnet and torch.cuda.is_available()

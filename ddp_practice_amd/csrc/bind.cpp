@@ -28,6 +28,7 @@ void register_ema(pybind11::module& m);
 void register_accum(pybind11::module& m);
 void register_conv_group(pybind11::module& m);
 void register_se(pybind11::module& m);
+void register_conv_dw(pybind11::module& m);
 }
 
 // sha1 of the sources this library was built from (build.py generates it; _ext.py compares
@@ -73,4 +74,5 @@ PYBIND11_MODULE(_C, m) {
   dpa::register_accum(m);
   dpa::register_conv_group(m);
   dpa::register_se(m);
+  dpa::register_conv_dw(m);
 }

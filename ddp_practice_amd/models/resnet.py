@@ -47,6 +47,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..amp import autocast, compute_dtype
+from ..ops import conv_dw as _dwconv
 from ..ops import conv_group as _gconv
 from ..ops import conv_igemm as _igemm
 from ..ops import se as _se
@@ -82,6 +83,9 @@ def _conv(x: torch.Tensor, conv: nn.Conv2d, cdtype: torch.dtype, bn: nn.Module |
     if _gconv.usable(x, conv, cdtype):
         # grouped 3x3 (ResNeXt) on the block-diagonal MFMA kernels; the BN takes its own statistics
         return _gconv.conv_group(x, conv.weight, conv.stride[0], conv.groups, cdtype), None
+    if _dwconv.usable(x, conv, cdtype):
+        # depthwise 3x3 (MobileNet) on the VALU granule kernels; the BN takes its own statistics
+        return _dwconv.conv_dw(x, conv.weight, conv.stride[0], cdtype), None
     w = conv.weight.to(cdtype)
     out = F.conv2d(x, w, None if conv.bias is None else conv.bias.to(cdtype), conv.stride, conv.padding,
                    conv.dilation, conv.groups)
