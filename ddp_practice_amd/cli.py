@@ -28,7 +28,10 @@ Additive flags (all optional; defaults reproduce the reference):
                                       se_resnet50 / se_resnext50_32x4d = the two with a
                                       squeeze-and-excitation gate per block (ops/se.py);
                                       mobilenet_v1 = MobileNetV1 on the same set (its depthwise
-                                      3x3 convs on ops/conv_dw.py)
+                                      3x3 convs on ops/conv_dw.py, its narrow pointwise convs on
+                                      ops/conv_pw.py)
+  --width-mult F                      mobilenet_v1: the width multiplier (0.25, 0.5, 0.75, ...; channel
+                                      counts rounded to multiples of 8; default 1.0)
   --lr / --momentum / --weight-decay  SGD hyper-parameters (defaults: the reference's SGD(params, 1e-4))
   --optimizer {sgd,adamw,adam}        adamw / adam: optim.AdamW / optim.Adam, one native launch per step whose
                                       step count lives on the device, so it replays from the step graph
@@ -101,6 +104,8 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
                              "resnext50_32x4d: ResNeXt-50 32x4d on the same images; "
                              "se_resnet50 / se_resnext50_32x4d: the two with squeeze-and-excitation gates; "
                              "mobilenet_v1: MobileNetV1 (depthwise-separable) on the same images")
+    parser.add_argument("--width-mult", type=float, default=1.0,
+                        help="mobilenet_v1: width multiplier (channel counts rounded to multiples of 8)")
     parser.add_argument("--lr", type=float, default=1e-4, help="SGD learning rate (the schedule's base rate)")
     parser.add_argument("--momentum", type=float, default=0.0)
     parser.add_argument("--weight-decay", type=float, default=0.0)
@@ -197,6 +202,27 @@ def lr_flags_default(args) -> bool:
     return (getattr(args, "lr", 1e-4) == 1e-4 and getattr(args, "momentum", 0.0) == 0.0
             and getattr(args, "weight_decay", 0.0) == 0.0 and getattr(args, "lr_schedule", "none") == "none"
             and getattr(args, "optimizer", "sgd") == "sgd" and getattr(args, "clip_grad_norm", 0.0) == 0.0)
+
+
+def model_flags(args) -> dict:
+    """The model constructor's keyword arguments beyond the common ones: --width-mult for mobilenet_v1;
+    exits on a width for another model and on a width that is not positive."""
+    wm = float(getattr(args, "width_mult", 1.0))
+    if getattr(args, "model", "convnet") != "mobilenet_v1":
+        if wm != 1.0:
+            raise SystemExit(f"error: --width-mult is mobilenet_v1's; --model {getattr(args, 'model', 'convnet')} has no widths")
+        return {}
+    if not wm > 0.0:
+        raise SystemExit(f"error: --width-mult expects a multiplier > 0, not {wm}")
+    return {"width_mult": wm}
+
+
+def build_model(args, amp_dtype=None, fused: bool = True):
+    """The ImageNet-shaped model ``--model`` names, with its flags (--num-classes, --width-mult)."""
+    from ddp_practice_amd import models as _models
+
+    return getattr(_models, args.model)(num_classes=args.num_classes, amp_dtype=amp_dtype, fused=fused,
+                                        **model_flags(args))
 
 
 def clip_flag(args) -> float | None:
@@ -372,6 +398,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     clip = clip_flag(args)
     ema_kw = ema_flags(args)
     accum = accum_flag(args)
+    model_flags(args)  # (exits on a contradiction before anything is built)
     import torch
 
     import ddp_practice_amd.distributed as dist
@@ -435,9 +462,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
     native = getattr(args, "impl", "native") == "native"
     # autocast inside forward, as the reference; fused=False: torch's own modules
     if resnet:
-        from ddp_practice_amd import models as _models
-
-        model = getattr(_models, args.model)(num_classes=args.num_classes, amp_dtype=amp, fused=native).to(dev)
+        model = build_model(args, amp, native).to(dev)
     else:
         model = ConvNet(amp_dtype=amp, fused=native).to(dev)
     if native:

@@ -29,6 +29,7 @@ void register_accum(pybind11::module& m);
 void register_conv_group(pybind11::module& m);
 void register_se(pybind11::module& m);
 void register_conv_dw(pybind11::module& m);
+void register_conv_pw(pybind11::module& m);
 }
 
 // sha1 of the sources this library was built from (build.py generates it; _ext.py compares
@@ -75,4 +76,5 @@ PYBIND11_MODULE(_C, m) {
   dpa::register_conv_group(m);
   dpa::register_se(m);
   dpa::register_conv_dw(m);
+  dpa::register_conv_pw(m);
 }

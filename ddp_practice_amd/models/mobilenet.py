@@ -11,8 +11,11 @@ Execution on a HIP device with bf16 / fp16 (``fused=True``): channels_last end t
   * every pointwise conv with C and Cout multiples of 64 runs on ``conv1x1`` with the
     following BN's statistics from the conv epilogue, and its data gradient takes the depthwise
     BN's backward sums (ops/bn_nhwc.BNTap), as ``Bottleneck`` does for bn2 -> conv3;
-  * the stem (C = 3) and the first pointwise conv (32 -> 64: C no multiple of 64) go through
-    the existing fallbacks of ``models/resnet.py::_conv`` / ``ops/conv1x1.py``;
+  * every other pointwise conv (32 -> 64 at width 1.0; at ``width_mult`` 0.75 / 0.5 / 0.25 the
+    24-, 48-, 96-, 16-, 32-, 8-channel ones) runs forward, data gradient and weight gradient on the
+    pointwise kernels (csrc/kernels/conv_pw.hip, ops/conv_pw.py; DPA_PWCONV=0: the torch.mm branch
+    of ``ops/conv1x1.py``); its BN takes its own statistics pass and bn1's BNTap is not consumed;
+  * the stem (C = 3) goes through the existing fallback of ``models/resnet.py::_conv``;
   * every BN runs on the native NHWC kernels with its ReLU (SyncBatchNorm when converted), the
     pool is the native global average pool and fc runs on the native MFMA linear kernels.
 On CPU, or with ``fused=False``, the plain torch modules run (the same math).

@@ -27,6 +27,9 @@ Execution on a HIP device (``fused=True``): activations are bf16/f16/f32
     forward, data gradient and weight gradient on the block-diagonal grouped kernels
     (csrc/kernels/conv_group.hip, ops/conv_group.py; DPA_GCONV=0: library path); the BN
     that follows takes its own statistics pass;
+  * a stride-1 1x1 conv whose C or Cout is no multiple of 64 (multiples of 8 up to 1024) runs
+    forward, data gradient and weight gradient on the pointwise kernels
+    (csrc/kernels/conv_pw.hip, ops/conv_pw.py; DPA_PWCONV=0: the torch.mm branch of ops/conv1x1.py);
   * squeeze-and-excitation (``se_reduction``; se_resnet50, se_resnext50_32x4d: Hu et al. 2018,
     timm's ``layerL.B.se.fc{1,2}`` keys): bn3 is applied without ReLU or residual, and the
     pool, the two fp32 gate layers (fp32 MFMA), the sigmoid, the channel scale, the residual add
@@ -50,6 +53,7 @@ from ..amp import autocast, compute_dtype
 from ..ops import conv_dw as _dwconv
 from ..ops import conv_group as _gconv
 from ..ops import conv_igemm as _igemm
+from ..ops import conv_pw as _pwconv
 from ..ops import se as _se
 from ..ops.conv1x1 import GradTap, conv1x1
 from ..ops.conv_nhwc import conv_nhwc
@@ -72,6 +76,11 @@ def _conv(x: torch.Tensor, conv: nn.Conv2d, cdtype: torch.dtype, bn: nn.Module |
     (a 1x1 conv's data gradient then also takes that BN's backward sums)."""
     want = bn if (bn is not None and bn.training) else None
     pk = _PACKS.get(id(conv))
+    if tap is None and xtap is None and _pwconv.usable(x, conv, cdtype):
+        # 1x1 with C or K no multiple of 64 (the narrow MobileNet widths) on the pointwise MFMA kernels
+        # instead of conv1x1's torch.mm branch.  Not done there: BN statistics in the epilogue (the BN
+        # takes its own pass) and the BNTap hand-off (``btap`` stays unfilled: the BN runs bwd_stats)
+        return _pwconv.conv_pw(x, conv.weight, cdtype), None
     if conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.groups == 1 and conv.bias is None:
         if want is None:
             return conv1x1(x, conv.weight, conv.stride[0], cdtype, tap, None, pk, xtap, btap), None
