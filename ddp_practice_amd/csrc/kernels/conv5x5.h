@@ -223,8 +223,10 @@ __host__ __device__ constexpr size_t conv5x5_dyn_bytes() {
 // halo it reads.  WR is the compile-time bound on that row count (conv5x5_win_rows of the
 // launch's nsplit: the launcher checks it); the per-lane trip counts of the staging pass and
 // its register arrays follow from it.  WR = H: every workgroup stages the whole image.
+// BR > 0 (PRO 1 / 2): the prologue's BN slab has exactly BR rows (pin.bn.nrows / bin.grows, checked
+// by the launcher): its loads take constant strides (strided_rowsum_n).  0: any row count.
 template <typename T, int CIN, int COUT, int H, int W, int MODE, int PRO = 0, int EPI = 0, int WPK = 0,
-          bool DYN = false, int WR = H, int ES = 0>
+          bool DYN = false, int WR = H, int ES = 0, int BR = 0>
 __device__ __forceinline__ void
 conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
              T* __restrict__ y, float* __restrict__ fslab, float* __restrict__ fstats,
@@ -606,7 +608,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
         }
       }
       load_wpk();
-      bn_finalize<CIN>(pin.bn, sc_s, beta_s, mean_s, istd_s, part, bid);
+      bn_finalize<CIN, RSUM_U, BR>(pin.bn, sc_s, beta_s, mean_s, istd_s, part, bid);
       DPA_STAMP(3);
 #pragma unroll
       for (int i = 0; i < IT8; ++i) {
@@ -655,7 +657,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
         }
       }
       load_wpk();
-      bn_finalize<CIN>(pin.bn, sc_s, beta_s, mean_s, istd_s, part, bid);
+      bn_finalize<CIN, RSUM_U, BR>(pin.bn, sc_s, beta_s, mean_s, istd_s, part, bid);
       DPA_STAMP(3);
 #pragma unroll
       for (int i = 0; i < IT; ++i) {
@@ -685,7 +687,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
       st.load(bin, b, r_lo);
       DPA_STAMP(8);
       load_wpk();
-      bn_bwd_coef<CIN, T>(bin, coef, part, sums, bid);
+      bn_bwd_coef<CIN, T, BR>(bin, coef, part, sums, bid);
       load_epi();
       DPA_STAMP(3);
       st.emit(coef, [&](int h, int ww, int c0, uint4 q00, uint4 q01, uint4 q10, uint4 q11) {
@@ -701,7 +703,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
       st.load(bin, b, r_lo);
       DPA_STAMP(8);
       load_wpk();
-      bn_bwd_coef<CIN, T>(bin, coef, part, sums, bid);
+      bn_bwd_coef<CIN, T, BR>(bin, coef, part, sums, bid);
       load_epi();
       DPA_STAMP(3);
       st.emit(coef, [&](int c, int h, int ww, T v00, T v01, T v10, T v11) {
@@ -899,7 +901,7 @@ conv5x5_body(const T* __restrict__ x, const float* __restrict__ w, const float* 
 }
 
 template <typename T, int CIN, int COUT, int H, int W, int MODE, int PRO = 0, int EPI = 0, int WPK = 0, int WR = H,
-          int ES = 0>
+          int ES = 0, int BR = 0>
 __global__ void __launch_bounds__(NTHR)
 conv5x5_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                T* __restrict__ y, float* __restrict__ fslab, float* __restrict__ fstats,
@@ -917,8 +919,8 @@ conv5x5_kernel(const T* __restrict__ x, const float* __restrict__ w, const float
       return;
     }
   }
-  conv5x5_body<T, CIN, COUT, H, W, MODE, PRO, EPI, WPK, false, WR, ES>(x, w, bias, y, fslab, fstats, shift, nsplit,
-                                                                       pin, bin, epi, wpk, pk, (int)blockIdx.x, gin);
+  conv5x5_body<T, CIN, COUT, H, W, MODE, PRO, EPI, WPK, false, WR, ES, BR>(x, w, bias, y, fslab, fstats, shift, nsplit,
+                                                                           pin, bin, epi, wpk, pk, (int)blockIdx.x, gin);
 }
 
 }  // namespace cb

@@ -54,8 +54,9 @@ struct WgradLds {
   static constexpr size_t bytes = o_wt + sizeof(float) * (STAGE ? (size_t)CL * NS : 4);
 };
 
+// BR > 0 (PRO 2): the BN backward slab has exactly BR rows (bin.grows, checked by the launcher).
 template <typename T, int CIN, int COUT, int H, int W, int ROWS, int PRO = 0, bool CHK = false, bool DYN = false,
-          int NSL = 0>
+          int NSL = 0, int BR = 0>
 __device__ __forceinline__ void
 conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ wslab, int nsplit,
                    const BwdIn<T>& bin, const int bid) {
@@ -177,7 +178,7 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
     } else {  // input rows r0-2 .. r0+ROWS+1 -> xpad (kw copies after the barrier below)
       stage_xpad();
     }
-    bn_bwd_coef<COUT, T>(bin, coef, part, sums, bid);
+    bn_bwd_coef<COUT, T, BR>(bin, coef, part, sums, bid);
     DPA_STAMP(3);
     st.emit(coef, [&](int co, int h, int ww, T v00, T v01, T v10, T v11) {
       dyl[co * DYS + h * WP + ww] = v00;
@@ -306,11 +307,11 @@ conv5x5_wgrad_body(const T* __restrict__ x, const T* __restrict__ dy, float* __r
   DPA_STAMP(7);
 }
 
-template <typename T, int CIN, int COUT, int H, int W, int ROWS, int PRO = 0>
+template <typename T, int CIN, int COUT, int H, int W, int ROWS, int PRO = 0, int BR = 0>
 __global__ void __launch_bounds__(NTHR)
 conv5x5_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ wslab,
                      int nsplit, BwdIn<T> bin = BwdIn<T>{}) {
-  conv5x5_wgrad_body<T, CIN, COUT, H, W, ROWS, PRO>(x, dy, wslab, nsplit, bin, (int)blockIdx.x);
+  conv5x5_wgrad_body<T, CIN, COUT, H, W, ROWS, PRO, false, false, 0, BR>(x, dy, wslab, nsplit, bin, (int)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------

@@ -202,6 +202,41 @@ __device__ __forceinline__ float strided_rowsum(const float* __restrict__ src, i
   return strided_rowsum(src, rows, RL, j, g, G, [] {});
 }
 
+// strided_rowsum of a slab whose row count is known at compile time (the step's own shapes: the
+// launcher checked rows == ROWS), G = NTHR / RL groups, one batch of U >= ROWS / G loads.  The same
+// values are added in the same order, so the sum is bitwise strided_rowsum<U>'s; what goes is the
+// address arithmetic.  Row g + u * G is in range for EVERY group while u < UF: those loads are
+// one 32-bit lane offset plus the constant u * G * RL * 4, no clamp, no 64-bit multiply-add, no
+// mask multiply.  The one u (if any) whose range depends on g keeps the clamped, masked form,
+// and the u past every group's range all add the same product, last row x 0, computed once (it
+// is added, not dropped: with a non-finite last row it is NaN, as in the runtime form).
+template <int RL, int U, int ROWS, typename F>
+__device__ __forceinline__ float strided_rowsum_n(const float* __restrict__ src, int j, int g, F&& after_issue) {
+  constexpr int G = NTHR / RL;
+  constexpr int UF = ROWS / G;            // u < UF: row g + u * G < ROWS for every g < G
+  constexpr int UP = (ROWS + G - 1) / G;  // u >= UP: out of range for every g
+  static_assert(ROWS > 0 && U >= UP, "one load batch holds the slab");
+  const int off = g * RL + j;
+  const int last = (ROWS - 1) * RL + j;
+  float v[U];
+#pragma unroll
+  for (int u = 0; u < UF; ++u) v[u] = src[off + u * G * RL];
+  if constexpr (UP > UF) {
+    const bool in = g + UF * G < ROWS;
+    v[UF] = src[in ? off + UF * G * RL : last] * (in ? 1.f : 0.f);
+  }
+  if constexpr (U > UP) {
+    const float z = src[last] * 0.f;
+#pragma unroll
+    for (int u = UP; u < U; ++u) v[u] = z;
+  }
+  after_issue();
+  float acc = 0.f;
+#pragma unroll
+  for (int u = 0; u < U; ++u) acc += v[u];
+  return acc;
+}
+
 // Sum of column j of a slab whose per-lane-group row sums sit in part[gg * RL + j] (lane
 // tid = g * RL + j wrote slot tid): the G = NTHR / RL groups are added in the order 0 .. G-1,
 // which fixes the bits.  Any lane may ask for any column after the barrier behind the writes:
@@ -221,7 +256,8 @@ __device__ __forceinline__ float group_colsum(const float* part, int j) {
 // kernel arguments, and the s_waitcnt vmcnt(0) before its use waited for every load the
 // kernel had issued so far (a whole memory round trip ahead of the slab loads, head .s).
 // U: rows per lane of the slab reduction's one load batch (strided_rowsum).
-template <int C, int U = RSUM_U>
+// ROWS > 0: bp.nrows == ROWS, checked by the launcher (strided_rowsum_n); 0: any row count.
+template <int C, int U = RSUM_U, int ROWS = 0>
 __device__ __forceinline__ void bn_finalize(const BNParams& bp, float* sc_s, float* beta_s, float* mean_s,
                                             float* istd_s, float* part, int bid) {
   const int tid = threadIdx.x, nthr = NTHR;
@@ -250,7 +286,8 @@ __device__ __forceinline__ void bn_finalize(const BNParams& bp, float* sc_s, flo
       if (xon && tid == 0) tk = xgmi::xsite_ticket(bp.xs, bid);
     };
     if (g < G) {
-      part[tid] = strided_rowsum<U>(bp.fslab, bp.nrows, RL, j, g, G, ticket);
+      if constexpr (ROWS > 0) part[tid] = strided_rowsum_n<RL, U, ROWS>(bp.fslab, j, g, ticket);
+      else part[tid] = strided_rowsum<U>(bp.fslab, bp.nrows, RL, j, g, G, ticket);
     } else {
       ticket();
       part[tid] = 0.f;
@@ -387,13 +424,15 @@ constexpr int bwd_rsum_u() { return C == 32 ? 8 : C == 16 ? 16 : RSUM_U; }
 // the whole (NTHR-thread) workgroup; part: >= NTHR floats of LDS.  One barrier, between the
 // lanes' row sums and the group adds; part is read after it and not written again.
 // (NTHR, not blockDim.x: see bn_finalize)
-template <int RL, int U, typename F>
+// ROWS > 0: rows == ROWS, checked by the launcher (strided_rowsum_n).
+template <int RL, int U, int ROWS = 0, typename F>
 __device__ __forceinline__ float colsum_lane(const float* __restrict__ src, int rows, float* part, F&& after_issue) {
   const int tid = threadIdx.x;
   constexpr int G = NTHR / RL;
   const int j = tid % RL, g = tid / RL;
   if (g < G) {
-    part[tid] = strided_rowsum<U>(src, rows, RL, j, g, G, after_issue);
+    if constexpr (ROWS > 0) part[tid] = strided_rowsum_n<RL, U, ROWS>(src, j, g, after_issue);
+    else part[tid] = strided_rowsum<U>(src, rows, RL, j, g, G, after_issue);
   } else {
     after_issue();
     part[tid] = 0.f;
@@ -414,7 +453,8 @@ __device__ __forceinline__ float colsum_lane(const float* __restrict__ src, int 
 // the same floats for its statistics partials after its compute barrier (conv5x5.h LS_IN_PART):
 // that barrier is what separates the two uses, so a caller must not keep anything in `part` past
 // it, nor write `part` between this function and it.
-template <int C, typename T, int U = bwd_rsum_u<C>()>
+// ROWS > 0: bi.grows == ROWS, checked by the launcher (the local rows keep the runtime form).
+template <int C, typename T, int ROWS = 0, int U = bwd_rsum_u<C>()>
 __device__ __forceinline__ void bn_bwd_coef(const BwdIn<T>& bi, float* coef, float* part, float* sums, int bid) {
   constexpr int RL = 2 * C;
   static_assert(RL <= NTHR, "one lane per slab column");
@@ -436,7 +476,7 @@ __device__ __forceinline__ void bn_bwd_coef(const BwdIn<T>& bi, float* coef, flo
   auto put = [&](float v) {
     if (tid < C) bi.dbeta[tid] = v; else bi.dgamma[tid - C] = v;
   };
-  float t = colsum_lane<RL, U>(bi.gsum, bi.grows, part, [] {});
+  float t = colsum_lane<RL, U, ROWS>(bi.gsum, bi.grows, part, [] {});
   if (xon) {  // (wave-uniform)
     if (tid < RL) sums[tid] = t;
     __syncthreads();

@@ -274,6 +274,19 @@ static void conv2_row_window(int wr, int nsplit, bool even, const char* what) {
 template <typename T>
 constexpr int kFwd2WR = conv2_wr<cb::kFwd2SplitT<T>, false>();
 
+// BN slab rows known at compile time (cb::strided_rowsum_n): the slabs of the step's batch, 32.
+// A launch whose slab has exactly that many rows runs the kernel instantiated for the count
+// (template parameter BR); any other row count runs BR = 0, the runtime form.
+constexpr int kStepB = 32;
+constexpr int kRowsFwd1 = kStepB * cb::SH<0>::SPLIT;     // fslab1: a row per conv1 forward workgroup
+constexpr int kRowsBwd2 = kStepB;                        // BN2 backward sums: a row per image
+constexpr int kRowsBwd1 = kStepB * cb::EPI_QUARTERS;     // BN1 backward sums: a row per image quarter
+template <int ROWS, typename F>  // f(std::integral_constant<int, BR>)
+static void with_slab_rows(int rows, F&& f) {
+  if (rows == ROWS) f(std::integral_constant<int, ROWS>{});
+  else f(std::integral_constant<int, 0>{});
+}
+
 // [BN1 -> ReLU -> pool1] -> conv2 (+ BN2 partial sums when training).
 void conv2_fwd(at::Tensor y1, c10::optional<at::Tensor> fslab1, at::Tensor fstats1, at::Tensor g1, at::Tensor b1,
                at::Tensor rm1, at::Tensor rv1, at::Tensor nbt1, double momentum, double eps, bool train, at::Tensor w2,
@@ -307,10 +320,12 @@ void conv2_fwd(at::Tensor y1, c10::optional<at::Tensor> fslab1, at::Tensor fstat
     constexpr int WR = kFwd2WR<T>;
     conv2_row_window(WR, ns, false, "conv2_fwd");
     if (train)
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 16, 32, 14, 14, 0, 1, 0, 1, WR>), dim3(B * ns), dim3(cb::NTHR), 0,
-                         stream, nullptr, nullptr, bias2.data_ptr<float>(), dptr<T>(y2), fslab2->data_ptr<float>(),
-                         fstats2.data_ptr<float>(), rm2.data_ptr<float>(), ns, pin, BwdIn<T>{}, BwdEpi<T>{},
-                         dptr<T>(wpk), cb::WPack<T>{});
+      with_slab_rows<kRowsFwd1>(bp.nrows, [&](auto br) {
+        hipLaunchKernelGGL((cb::conv5x5_kernel<T, 16, 32, 14, 14, 0, 1, 0, 1, WR, 0, decltype(br)::value>),
+                           dim3(B * ns), dim3(cb::NTHR), 0, stream, nullptr, nullptr, bias2.data_ptr<float>(),
+                           dptr<T>(y2), fslab2->data_ptr<float>(), fstats2.data_ptr<float>(), rm2.data_ptr<float>(),
+                           ns, pin, BwdIn<T>{}, BwdEpi<T>{}, dptr<T>(wpk), cb::WPack<T>{});
+      });
     else
       hipLaunchKernelGGL((cb::conv5x5_kernel<T, 16, 32, 14, 14, 1, 1, 0, 1, WR>), dim3(B * ns), dim3(cb::NTHR), 0,
                          stream, nullptr, nullptr, bias2.data_ptr<float>(), dptr<T>(y2), nullptr, nullptr, nullptr,
@@ -546,12 +561,12 @@ static void with_dgrad_split(int ds, F&& f) {
 template <int S>
 constexpr int kDgrad2WR = conv2_wr<S, true>();  // whole 2x2 windows: even rows
 // the data-gradient role's kernel body, one spelling for every launch that hosts it
-template <typename T, bool DYN, int S>
+template <typename T, bool DYN, int S, int BR = 0>
 __device__ __forceinline__ void conv2_dgrad_role(const T* __restrict__ wpk_d, T* __restrict__ dp1,
                                                  const BwdIn<T>& bi_d, const BwdEpi<T>& ep, int bid) {
-  cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1, DYN, kDgrad2WR<S>, S>(nullptr, nullptr, nullptr, dp1, nullptr,
-                                                                        nullptr, nullptr, S, PoolIn<T>{}, bi_d, ep,
-                                                                        wpk_d, cb::WPack<T>{}, bid);
+  cb::conv5x5_body<T, 32, 16, 14, 14, 2, 2, 1, 1, DYN, kDgrad2WR<S>, S, BR>(nullptr, nullptr, nullptr, dp1, nullptr,
+                                                                            nullptr, nullptr, S, PoolIn<T>{}, bi_d,
+                                                                            ep, wpk_d, cb::WPack<T>{}, bid);
 }
 // rows of bslab1: one per image quarter, whatever the dtype and the split
 int64_t dgrad2_rows(int64_t B, bool fp32) {
@@ -583,9 +598,11 @@ void conv2_dgrad(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx
     with_dgrad_split<T>(ds, [&](auto sc) {
       constexpr int S = decltype(sc)::value;
       conv2_row_window(kDgrad2WR<S>, S, true, "conv2_dgrad");
-      hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<S>, S>), dim3(B * S),
-                         dim3(cb::NTHR), 0, cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr, nullptr,
-                         nullptr, S, PoolIn<T>{}, bi, ep, dptr<T>(wpk_d), cb::WPack<T>{});
+      with_slab_rows<kRowsBwd2>(bi.grows, [&](auto br) {
+        hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<S>, S, decltype(br)::value>),
+                           dim3(B * S), dim3(cb::NTHR), 0, cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1),
+                           nullptr, nullptr, nullptr, S, PoolIn<T>{}, bi, ep, dptr<T>(wpk_d), cb::WPack<T>{});
+      });
     });
   });
   DPA_CHECK_LAUNCH();
@@ -614,19 +631,20 @@ int64_t wgrad_bn_rows(int64_t layer, int64_t B);
 static int64_t wgrad2_wgs(int64_t B) { return B * WG2_PER_IMG; }
 
 // the conv2 weight-gradient role of one workgroup (bid within the role)
-template <typename T, bool DYN>
+template <typename T, bool DYN, int BR = 0>
 __device__ __forceinline__ void conv2_wgrad_role(const T* __restrict__ p1, float* __restrict__ wslab2,
                                                  const BwdIn<T>& bi_w, int bid) {
-  cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, 14, 2, false, DYN, WG2_NSL>(p1, nullptr, wslab2, WG2_PER_IMG, bi_w, bid);
+  cb::conv5x5_wgrad_body<T, 16, 32, 14, 14, 14, 2, false, DYN, WG2_NSL, BR>(p1, nullptr, wslab2, WG2_PER_IMG, bi_w,
+                                                                            bid);
 }
 template <typename T>
 constexpr size_t conv2_wgrad_lds() {
   return cb::WgradLds<T, 16, 32, 14, 14, 14, WG2_NSL>::bytes;
 }
-template <typename T>
+template <typename T, int BR = 0>
 __global__ void __launch_bounds__(cb::NTHR)
 conv2_wgrad_kernel(const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w) {
-  conv2_wgrad_role<T, false>(p1, wslab2, bi_w, (int)blockIdx.x);
+  conv2_wgrad_role<T, false, BR>(p1, wslab2, bi_w, (int)blockIdx.x);
 }
 // fc weight / bias gradient of the per-image head (csrc/kernels/convnet_head.hip): the head's
 // one reduction over the batch, computed by extra workgroups of the conv2 backward launch
@@ -706,15 +724,15 @@ __device__ __forceinline__ void fc_wgrad_body(const FcW<T>& f, int wg) {
 template <typename T>
 __global__ void __launch_bounds__(cb::NTHR) fc_wgrad_kernel(FcW<T> f) { fc_wgrad_body<T>(f, (int)blockIdx.x); }
 
-template <typename T, int S>
+template <typename T, int S, int BR = 0>  // BR: both roles read the same BN2 backward slab
 __global__ void __launch_bounds__(cb::NTHR)
 conv2_bwd_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d, BwdEpi<T> ep,
                  const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int ndg, int nwg, FcW<T> fw) {
   const int bid = (int)blockIdx.x;
   if (bid < ndg)
-    conv2_dgrad_role<T, false, S>(wpk_d, dp1, bi_d, ep, bid);
+    conv2_dgrad_role<T, false, S, BR>(wpk_d, dp1, bi_d, ep, bid);
   else if (bid < ndg + nwg)
-    conv2_wgrad_role<T, false>(p1, wslab2, bi_w, bid - ndg);
+    conv2_wgrad_role<T, false, BR>(p1, wslab2, bi_w, bid - ndg);
   else
     fc_wgrad_body<T>(fw, bid - ndg - nwg);
 }
@@ -725,16 +743,16 @@ conv2_bwd_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d
 // the static arrays, which does not fit a CU's 160 KB -- the reason fp32 ran the data
 // gradient and the weight gradient as two launches, one after the other, each on at
 // most half the CUs (profiles/r6g_cn_steady_fp32.txt: 16.7 + 15.2 us).
-template <typename T, int S>
+template <typename T, int S, int BR = 0>
 __global__ void __launch_bounds__(cb::NTHR)
 conv2_bwd_dyn_kernel(const T* __restrict__ wpk_d, T* __restrict__ dp1, BwdIn<T> bi_d, BwdEpi<T> ep,
                      const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int ndg, int nwg,
                      FcW<T> fw) {
   const int bid = (int)blockIdx.x;
   if (bid < ndg)
-    conv2_dgrad_role<T, true, S>(wpk_d, dp1, bi_d, ep, bid);
+    conv2_dgrad_role<T, true, S, BR>(wpk_d, dp1, bi_d, ep, bid);
   else if (bid < ndg + nwg)
-    conv2_wgrad_role<T, true>(p1, wslab2, bi_w, bid - ndg);
+    conv2_wgrad_role<T, true, BR>(p1, wslab2, bi_w, bid - ndg);
   else
     fc_wgrad_body<T>(fw, bid - ndg - nwg);
 }
@@ -750,8 +768,11 @@ static bool fp32_merged_bwd() {
     const char* e = std::getenv("DPA_FP32_MERGED_BWD");
     if (e != nullptr && std::atoi(e) == 0) return false;
     const size_t b = conv2_bwd_dyn_bytes<float>();
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<float, 4>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)b) == hipSuccess;
+    bool ok = true;
+    for (const void* k : {reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<float, 4>),
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<float, 4, kRowsBwd2>)})
+      ok = ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b) == hipSuccess;
+    return ok;
   }();
   return on;
 }
@@ -768,7 +789,11 @@ static bool lp_dyn_bwd() {
     for (const void* k : {reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__hip_bfloat16, 2>),
                           reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__hip_bfloat16, 4>),
                           reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__half, 2>),
-                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__half, 4>)})
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__half, 4>),
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__hip_bfloat16, 2, kRowsBwd2>),
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__hip_bfloat16, 4, kRowsBwd2>),
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__half, 2, kRowsBwd2>),
+                          reinterpret_cast<const void*>(&conv2_bwd_dyn_kernel<__half, 4, kRowsBwd2>)})
       ok = ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)std::max(conv2_bwd_dyn_bytes<__hip_bfloat16>(),
                                                    conv2_bwd_dyn_bytes<__half>())) == hipSuccess;
@@ -781,12 +806,12 @@ static bool conv2_bwd_dyn() { return std::is_same<T, float>::value ? fp32_merged
 
 // fp32 without the merged launch: the conv2 weight-gradient role and the fc weight gradient
 // in one launch (the data-gradient role's static LDS does not fit beside the weight gradient's)
-template <typename T>
+template <typename T, int BR = 0>
 __global__ void __launch_bounds__(cb::NTHR)
 conv2_wgrad_fc_kernel(const T* __restrict__ p1, float* __restrict__ wslab2, BwdIn<T> bi_w, int nwg, FcW<T> fw) {
   const int bid = (int)blockIdx.x;
   if (bid < nwg)
-    conv2_wgrad_role<T, false>(p1, wslab2, bi_w, bid);
+    conv2_wgrad_role<T, false, BR>(p1, wslab2, bi_w, bid);
   else
     fc_wgrad_body<T>(fw, bid - nwg);
 }
@@ -882,25 +907,28 @@ void conv2_bwd(at::Tensor wpk_d, at::Tensor y2, at::Tensor dp2, at::Tensor idx2,
     with_dgrad_split<T>(ds, [&](auto sc) {
       constexpr int S = decltype(sc)::value;
       conv2_row_window(kDgrad2WR<S>, S, true, "conv2_bwd data gradient");
-      if (conv2_bwd_dyn<T>()) {  // one launch, the roles' tiles in dynamic LDS (the largest role's bytes)
-        hipLaunchKernelGGL((conv2_bwd_dyn_kernel<T, S>), dim3(ndg + nwg + nfc), dim3(cb::NTHR),
-                           conv2_bwd_dyn_bytes<T>(), cur_stream(), dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1),
-                           wslab2.data_ptr<float>(), bw, ndg, nwg, fw);
-      } else if constexpr (std::is_same<T, float>::value) {
-        // fp32 static tiles: the two roles' LDS (173 KB) exceed one CU's 160 KB -> separate launches
-        // (the fc weight gradient: extra workgroups of the weight-gradient launch; its site's
-        // tickets are the nwg conv workgroups', set above)
-        bd.xs.nblk = 0;  // the data-gradient launch is its site's whole grid (ndg: checked above)
-        hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<S>, S>), dim3(ndg),
-                           dim3(cb::NTHR), 0, cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr, nullptr,
-                           nullptr, S, PoolIn<T>{}, bd, ep, dptr<T>(wpk_d), cb::WPack<T>{});
-        hipLaunchKernelGGL(conv2_wgrad_fc_kernel<T>, dim3(nwg + nfc), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(p1),
-                           wslab2.data_ptr<float>(), bw, nwg, fw);
-      } else {
-        hipLaunchKernelGGL((conv2_bwd_kernel<T, S>), dim3(ndg + nwg + nfc), dim3(cb::NTHR), 0, cur_stream(),
-                           dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(), bw, ndg, nwg,
-                           fw);
-      }
+      with_slab_rows<kRowsBwd2>(bd.grows, [&](auto br) {
+        constexpr int BR = decltype(br)::value;
+        if (conv2_bwd_dyn<T>()) {  // one launch, the roles' tiles in dynamic LDS (the largest role's bytes)
+          hipLaunchKernelGGL((conv2_bwd_dyn_kernel<T, S, BR>), dim3(ndg + nwg + nfc), dim3(cb::NTHR),
+                             conv2_bwd_dyn_bytes<T>(), cur_stream(), dptr<T>(wpk_d), dptr<T>(dp1), bd, ep,
+                             dptr<T>(p1), wslab2.data_ptr<float>(), bw, ndg, nwg, fw);
+        } else if constexpr (std::is_same<T, float>::value) {
+          // fp32 static tiles: the two roles' LDS (173 KB) exceed one CU's 160 KB -> separate launches
+          // (the fc weight gradient: extra workgroups of the weight-gradient launch; its site's
+          // tickets are the nwg conv workgroups', set above)
+          bd.xs.nblk = 0;  // the data-gradient launch is its site's whole grid (ndg: checked above)
+          hipLaunchKernelGGL((cb::conv5x5_kernel<T, 32, 16, 14, 14, 2, 2, 1, 1, kDgrad2WR<S>, S, BR>), dim3(ndg),
+                             dim3(cb::NTHR), 0, cur_stream(), nullptr, nullptr, nullptr, dptr<T>(dp1), nullptr,
+                             nullptr, nullptr, S, PoolIn<T>{}, bd, ep, dptr<T>(wpk_d), cb::WPack<T>{});
+          hipLaunchKernelGGL((conv2_wgrad_fc_kernel<T, BR>), dim3(nwg + nfc), dim3(cb::NTHR), 0, cur_stream(),
+                             dptr<T>(p1), wslab2.data_ptr<float>(), bw, nwg, fw);
+        } else {
+          hipLaunchKernelGGL((conv2_bwd_kernel<T, S, BR>), dim3(ndg + nwg + nfc), dim3(cb::NTHR), 0, cur_stream(),
+                             dptr<T>(wpk_d), dptr<T>(dp1), bd, ep, dptr<T>(p1), wslab2.data_ptr<float>(), bw, ndg,
+                             nwg, fw);
+        }
+      });
     });
   });
   DPA_CHECK_LAUNCH();
@@ -935,13 +963,18 @@ void conv_wgrad_bn(at::Tensor x, at::Tensor y, at::Tensor dp, at::Tensor idx, at
     }
     if (cin == 16 && cout == 32 && H == 14) {
       TORCH_CHECK(wslab.numel() == wgrad_bn_rows(2, B) * (32 * 400 + 32), "wgrad slab size");
-      hipLaunchKernelGGL(conv2_wgrad_kernel<T>, dim3((int)wgrad2_wgs(B)), dim3(cb::NTHR), 0, cur_stream(),
-                         dptr<T>(x), wslab.data_ptr<float>(), bi);
+      with_slab_rows<kRowsBwd2>(bi.grows, [&](auto br) {
+        hipLaunchKernelGGL((conv2_wgrad_kernel<T, decltype(br)::value>), dim3((int)wgrad2_wgs(B)), dim3(cb::NTHR), 0,
+                           cur_stream(), dptr<T>(x), wslab.data_ptr<float>(), bi);
+      });
     } else if (cin == 1 && cout == 16 && H == 28) {
       constexpr int ns = (28 + WG1_ROWS - 1) / WG1_ROWS;
       TORCH_CHECK(wslab.numel() == (int64_t)B * ns * (16 * 25 + 16), "wgrad slab size");
-      hipLaunchKernelGGL((cb::conv5x5_wgrad_kernel<T, 1, 16, 28, 28, WG1_ROWS, 2>), dim3(B * ns), dim3(cb::NTHR),
-                         0, cur_stream(), dptr<T>(x), nullptr, wslab.data_ptr<float>(), ns, bi);
+      with_slab_rows<kRowsBwd1>(bi.grows, [&](auto br) {
+        hipLaunchKernelGGL((cb::conv5x5_wgrad_kernel<T, 1, 16, 28, 28, WG1_ROWS, 2, decltype(br)::value>),
+                           dim3(B * ns), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x), nullptr,
+                           wslab.data_ptr<float>(), ns, bi);
+      });
     } else {
       TORCH_CHECK(false, "fused wgrad: shape not instantiated");
     }
@@ -956,13 +989,14 @@ void conv_wgrad_bn(at::Tensor x, at::Tensor y, at::Tensor dp, at::Tensor idx, at
 // slab_reduce launch.  A reduction workgroup owns SLAB2_K chunks of 16 columns (the conv2
 // slab has one row per image: few rows per lane, so more columns per lane instead).
 constexpr int SLAB2_K = 4;
-template <typename T>
+template <typename T, int BR = 0>
 __global__ void __launch_bounds__(cb::NTHR)
 wgrad1_slab2_kernel(const T* __restrict__ x, float* __restrict__ wslab1, BwdIn<T> bi, int nwg1,
                     const float* __restrict__ wslab2, int rows2, int n2, float* __restrict__ out2, GradChk rc) {
   constexpr int ns = (28 + WG1_ROWS_ - 1) / WG1_ROWS_;
   if ((int)blockIdx.x < nwg1)
-    cb::conv5x5_wgrad_body<T, 1, 16, 28, 28, WG1_ROWS_, 2, true>(x, nullptr, wslab1, ns, bi, (int)blockIdx.x);
+    cb::conv5x5_wgrad_body<T, 1, 16, 28, 28, WG1_ROWS_, 2, true, false, 0, BR>(x, nullptr, wslab1, ns, bi,
+                                                                               (int)blockIdx.x);
   else
     cb::slab_reduce_chunks_body<SLAB2_K>(wslab2, rows2, n2, out2, (int)blockIdx.x - nwg1, rc);
 }
@@ -996,9 +1030,11 @@ void conv1_wgrad_slab2(at::Tensor x, at::Tensor y1, at::Tensor dp1, at::Tensor i
       bi.chk_rows = 1;
       bi.chk_row_bound = rc.bound / (float)nwg1;
     }
-    hipLaunchKernelGGL(wgrad1_slab2_kernel<T>, dim3(nwg1 + nred), dim3(cb::NTHR), 0, cur_stream(), dptr<T>(x),
-                       wslab1.data_ptr<float>(), bi, nwg1, wslab2.data_ptr<float>(), rows2, N2,
-                       out2.data_ptr<float>(), rc);
+    with_slab_rows<kRowsBwd1>(bi.grows, [&](auto br) {
+      hipLaunchKernelGGL((wgrad1_slab2_kernel<T, decltype(br)::value>), dim3(nwg1 + nred), dim3(cb::NTHR), 0,
+                         cur_stream(), dptr<T>(x), wslab1.data_ptr<float>(), bi, nwg1, wslab2.data_ptr<float>(), rows2,
+                         N2, out2.data_ptr<float>(), rc);
+    });
   });
   DPA_CHECK_LAUNCH();
 }

@@ -95,7 +95,8 @@ __device__ __forceinline__ float unpack16(unsigned short bits) {
 // (cb::pack_fc: [256 lanes][NM][8] of T, already rounded, padding zero): NM 16-B loads per lane
 // instead of NM * 7 scalar f32 loads, and no rounding pass.  Same values, same accumulation
 // order: every output is bitwise what the unpacked kernel gives.
-template <typename T, int NM, int NT, bool PK = false>
+// ROWS > 0: the BN2 slab has exactly ROWS rows (head_step checks; cb::strided_rowsum_n), 0: any.
+template <typename T, int NM, int NT, bool PK = false, int ROWS = 0>
 __global__ void __launch_bounds__(NT)
 head_row_kernel(const T* __restrict__ y, BNParams bn, const float* __restrict__ wfc, const float* __restrict__ bfc,
                 T* __restrict__ logits, T* __restrict__ p_out, uint8_t* __restrict__ idx_out,
@@ -118,15 +119,38 @@ head_row_kernel(const T* __restrict__ y, BNParams bn, const float* __restrict__ 
   // 1. every load of the kernel up front.  Unconditional (clamped index, discarded by a
   //    multiply): a conditional load into a register array is branched around and waited
   //    for one by one (head_step .s, ROCm 7.2).
+  //    Feature k = tid + i * NT is (channel, position) = (k / PP, k % PP): one division for i = 0,
+  //    then NT = DC * PP + DJ steps the pair (256 = 5 * 49 + 11), and position / 7 is a
+  //    multiply-shift that is exact below 49 -- no general division per feature, one 32-bit
+  //    element offset from the image base per load pair.  The last iteration's k is clamped to
+  //    K - 1 = (C - 1, PP - 1).  fc[i] keeps the channel for phase 2.
+  constexpr int DC = NT / PP, DJ = NT % PP;
+  static_assert((IT - 2) * NT + NT - 1 < K, "only the last iteration runs past K");
+  static_assert((6 * 37 >> 8) == 0 && (7 * 37 >> 8) == 1 && (13 * 37 >> 8) == 1 && (14 * 37 >> 8) == 2 &&
+                (20 * 37 >> 8) == 2 && (21 * 37 >> 8) == 3 && (27 * 37 >> 8) == 3 && (28 * 37 >> 8) == 4 &&
+                (34 * 37 >> 8) == 4 && (35 * 37 >> 8) == 5 && (41 * 37 >> 8) == 5 && (42 * 37 >> 8) == 6 &&
+                (48 * 37 >> 8) == 6 && WO == 7 && PP == 49, "j * 37 >> 8 == j / 7 for j < 49");
   const T* yb = y + (size_t)b * C * H * W;
   P top[IT], bot[IT];
+  int fc[IT];
+  {
+    int c = tid / PP, j = tid - c * PP;
 #pragma unroll
-  for (int i = 0; i < IT; ++i) {
-    const int k = min(tid + i * NT, K - 1);
-    const int c = k / PP, j = k % PP, ho = j / WO, wo = j % WO;
-    const P* src = reinterpret_cast<const P*>(yb + ((size_t)c * H + 2 * ho) * W + 2 * wo);
-    top[i] = src[0];
-    bot[i] = src[W / 2];
+    for (int i = 0; i < IT; ++i) {
+      const bool past = i == IT - 1 && tid + i * NT > K - 1;  // the clamp on k
+      const int cc = past ? C - 1 : c, jj = past ? PP - 1 : j;
+      const int ho = (jj * 37) >> 8, wo = jj - WO * ho;
+      const P* src = reinterpret_cast<const P*>(yb + ((cc * H + 2 * ho) * W + 2 * wo));
+      top[i] = src[0];
+      bot[i] = src[W / 2];
+      fc[i] = cc;
+      j += DJ;
+      c += DC;
+      if (j >= PP) {
+        j -= PP;
+        ++c;
+      }
+    }
   }
   float wq[NM][IT];  // fc weights of this lane's features, every class
   u16x8 wraw[PK ? NM : 1];  // PK: the packed granules (this lane's class rows)
@@ -153,7 +177,7 @@ head_row_kernel(const T* __restrict__ y, BNParams bn, const float* __restrict__ 
   // lane groups: the one load batch holds batch 32 at either split count (64 | 128 rows).
   // Not the 1024-lane form: its 128-VGPR budget has no room for the taller batch (it spilt).
   constexpr int RU = NT == 256 && cb::kFwd2SplitT<T> > 2 ? (32 * cb::kFwd2SplitT<T> + 2) / 3 : cb::RSUM_U;
-  cb::bn_finalize<C, RU>(bn, sc_s, beta_s, mean_s, istd_s, part_s, b);  // ends with a barrier
+  cb::bn_finalize<C, RU, ROWS>(bn, sc_s, beta_s, mean_s, istd_s, part_s, b);  // ends with a barrier
   DPA_STAMP(2);
   if (hr.chk != nullptr && b == 0 && tid == 0) {  // the step's gradient-check words (GradChk)
     hr.chk[0] = 0;
@@ -165,7 +189,7 @@ head_row_kernel(const T* __restrict__ y, BNParams bn, const float* __restrict__ 
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     const int k = tid + i * NT;
-    const int c = min(k, K - 1) / PP;
+    const int c = fc[i];
     float best, xh;
     int bi;
     cb::bn_relu_max4x<T>(top[i], bot[i], sc_s[c], beta_s[c], mean_s[c], istd_s[c], best, bi, xh);
@@ -434,8 +458,13 @@ void head_step(at::Tensor y2, at::Tensor fslab2, at::Tensor fstats2, at::Tensor 
     }();
     // 16-class tiles stay at 256 lanes (at 1024 the 128-VGPR budget spills them)
     const int ntl = N <= 10 ? nt : 256;
-    auto kern = N > 10 ? head_row_kernel<T, NMAX, 256>
-                       : (nt == 256 ? head_row_kernel<T, 10, 256> : head_row_kernel<T, 10, NT_MAX>);
+    // the step's own slab (batch 32: one row per conv2 forward workgroup) takes the 256-lane
+    // kernels whose BN2 finalize knows the row count; any other slab the runtime form
+    constexpr int FR = 32 * cb::kFwd2SplitT<T>;
+    const bool fr = bp.nrows == FR && ntl == 256;
+    auto kern = N > 10 ? (fr ? head_row_kernel<T, NMAX, 256, false, FR> : head_row_kernel<T, NMAX, 256>)
+                       : (nt == 256 ? (fr ? head_row_kernel<T, 10, 256, false, FR> : head_row_kernel<T, 10, 256>)
+                                    : head_row_kernel<T, 10, NT_MAX>);
     const T* pkp = nullptr;
     if (wfc_pk.has_value()) {  // the fc weights packed by this step's conv1 launch (cb::pack_fc)
       DPA_CHECK_INPUT(*wfc_pk);
@@ -444,7 +473,8 @@ void head_step(at::Tensor y2, at::Tensor fslab2, at::Tensor fstats2, at::Tensor 
         TORCH_CHECK(wfc_pk->scalar_type() == y2.scalar_type() && wfc_pk->numel() == cb::fcp_len(cb::fcp_nm(N)),
                     "head_step: wfc_pk holds [256][", cb::fcp_nm(N), "][8] elements of the compute dtype");
         pkp = dptr<T>(*wfc_pk);
-        kern = N > 10 ? head_row_kernel<T, NMAX, 256, true> : head_row_kernel<T, 10, 256, true>;
+        kern = N > 10 ? (fr ? head_row_kernel<T, NMAX, 256, true, FR> : head_row_kernel<T, NMAX, 256, true>)
+                      : (fr ? head_row_kernel<T, 10, 256, true, FR> : head_row_kernel<T, 10, 256, true>);
       } else {
         TORCH_CHECK(false, "head_step: packed fc weights are bf16 / fp16 only");
       }
