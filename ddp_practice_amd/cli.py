@@ -19,7 +19,7 @@ Additive flags (all optional; defaults reproduce the reference):
                                       autocast, GradScaler, SGD, SyncBatchNorm and DDP
                                       (parity / same-node baseline runs)
   --seed N                            model-init seed
-  --model {convnet,resnet50,resnext50_32x4d,se_resnet50,se_resnext50_32x4d,mobilenet_v1}
+  --model {convnet,resnet50,resnext50_32x4d,se_resnet50,se_resnext50_32x4d,mobilenet_v1,mnasnet1_0}
                                       resnet50 = BASELINE.json config 5 (ResNet-50, torchvision
                                       layout) on a synthetic ImageNet-shaped set
                                       (--image-size, --num-classes; data/imagenet.py);
@@ -29,7 +29,9 @@ Additive flags (all optional; defaults reproduce the reference):
                                       squeeze-and-excitation gate per block (ops/se.py);
                                       mobilenet_v1 = MobileNetV1 on the same set (its depthwise
                                       3x3 convs on ops/conv_dw.py, its narrow pointwise convs on
-                                      ops/conv_pw.py)
+                                      ops/conv_pw.py);
+                                      mnasnet1_0 = MnasNet-B1 (torchvision's layout) on the same set
+                                      (its 5x5 depthwise convs on csrc/kernels/conv_dw5.hip)
   --width-mult F                      mobilenet_v1: the width multiplier (0.25, 0.5, 0.75, ...; channel
                                       counts rounded to multiples of 8; default 1.0)
   --lr / --momentum / --weight-decay  SGD hyper-parameters (defaults: the reference's SGD(params, 1e-4))
@@ -99,11 +101,12 @@ def add_run_args(parser, amp_default: str, checkpoint: str, distributed: bool) -
                         help="torch: run the same program on PyTorch's own stack (parity / baseline)")
     parser.add_argument("--model", default="convnet",
                         choices=["convnet", "resnet50", "resnext50_32x4d", "se_resnet50", "se_resnext50_32x4d",
-                                 "mobilenet_v1"],
+                                 "mobilenet_v1", "mnasnet1_0"],
                         help="resnet50: ResNet-50 on synthetic 3 x S x S images (BASELINE.json config 5); "
                              "resnext50_32x4d: ResNeXt-50 32x4d on the same images; "
                              "se_resnet50 / se_resnext50_32x4d: the two with squeeze-and-excitation gates; "
-                             "mobilenet_v1: MobileNetV1 (depthwise-separable) on the same images")
+                             "mobilenet_v1: MobileNetV1 (depthwise-separable) on the same images; "
+                             "mnasnet1_0: MnasNet-B1 (inverted residuals, 3x3 and 5x5 depthwise) on the same images")
     parser.add_argument("--width-mult", type=float, default=1.0,
                         help="mobilenet_v1: width multiplier (channel counts rounded to multiples of 8)")
     parser.add_argument("--lr", type=float, default=1e-4, help="SGD learning rate (the schedule's base rate)")
@@ -420,7 +423,7 @@ def run(args, distributed: bool, local_rank: int = 0, generator_seed: int | None
 
     # an ImageNet-shaped model: the synthetic image set, --image-size / --num-classes, one step per graph
     resnet = getattr(args, "model", "convnet") in ("resnet50", "resnext50_32x4d", "se_resnet50",
-                                                   "se_resnext50_32x4d", "mobilenet_v1")
+                                                   "se_resnext50_32x4d", "mobilenet_v1", "mnasnet1_0")
     from ddp_practice_amd.data.mnist import idx_available
 
     on_device = (not resnet and torch.cuda.is_available()

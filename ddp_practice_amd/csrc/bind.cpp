@@ -29,6 +29,7 @@ void register_accum(pybind11::module& m);
 void register_conv_group(pybind11::module& m);
 void register_se(pybind11::module& m);
 void register_conv_dw(pybind11::module& m);
+void register_conv_dw5(pybind11::module& m);
 void register_conv_pw(pybind11::module& m);
 }
 
@@ -76,5 +77,6 @@ PYBIND11_MODULE(_C, m) {
   dpa::register_conv_group(m);
   dpa::register_se(m);
   dpa::register_conv_dw(m);
+  dpa::register_conv_dw5(m);
   dpa::register_conv_pw(m);
 }

@@ -69,7 +69,7 @@
 //                the same bits on the same inputs.  wgrad_splits keeps about 1024 workgroups and
 //                caps the partials at the activation bytes, as the grouped one.
 // No BN statistics in the epilogue (the following BN takes its own pass) and no tap hand-off.
-#include "common.h"
+#include "conv_dw_gran.h"
 
 #include <map>
 #include <mutex>
@@ -78,47 +78,12 @@
 namespace dpa {
 namespace dwconv {
 
-constexpr int CB = 64;  // channels per workgroup
-constexpr int NG = 8;   // granules (8 channels, 16 B) per channel block
-constexpr int PS = 72;  // LDS pixel stride, elements
 constexpr int DXT = 16;  // stride-2 data gradient: dx tile side
 constexpr int DD = DXT / 2 + 1;  // ... and the dy pixels under it, per side
 
 template <int S> struct Tile;  // output tile per stride (NG * TW * row groups = 256 threads)
 template <> struct Tile<1> { static constexpr int TH = 8, TW = 16; };
 template <> struct Tile<2> { static constexpr int TH = 8, TW = 8; };
-
-typedef unsigned short lds_t;  // LDS arrays are raw 16-bit words
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-// ---- granules ----------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ void unpack(u32x4 v, float (&f)[8]);
-template <> __device__ __forceinline__ void unpack<__hip_bfloat16>(u32x4 v, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __builtin_bit_cast(float, v[i] << 16);
-    f[2 * i + 1] = __builtin_bit_cast(float, v[i] & 0xffff0000u);
-  }
-}
-template <> __device__ __forceinline__ void unpack<__half>(u32x4 v, float (&f)[8]) {
-  const f16x8 h = __builtin_bit_cast(f16x8, v);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) f[i] = (float)h[i];
-}
-template <typename T> __device__ __forceinline__ void ld_gran(const lds_t* p, float (&f)[8]) {
-  unpack<T>(*reinterpret_cast<const u32x4*>(p), f);
-}
-// eight fp32 values -> one rounding each -> one 16-B store
-template <typename T> __device__ __forceinline__ void st_gran(T* p, const float (&f)[8]) {
-  typedef typename MM<T>::elem E;
-  u16x8 v;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const E e = MM<T>::cv(f[i]);
-    v[i] = __builtin_bit_cast(unsigned short, e);
-  }
-  *reinterpret_cast<u16x8*>(p) = v;
-}
 
 // The granule's 8 x 9 fp32 weights (72 contiguous floats from channel c), rounded to T, as
 // wr[tap][channel]; FLIP: tap 8 - tap (the stride-1 data gradient).  A masked granule reads
@@ -136,23 +101,6 @@ __device__ __forceinline__ void load_weights(float (&wr)[9][8], const float* __r
   for (int j = 0; j < 8; ++j)
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) wr[FLIP ? 8 - tap : tap][j] = MM<T>::rnd(flat[j * 9 + tap]);
-}
-
-// RH x RW pixels x ng granules of image n from (h0, w0) of an [N][H][W][C] tensor; zeros
-// outside [0, H) x [0, W) and in the masked granules.
-template <typename T, int RH, int RW>
-__device__ __forceinline__ void stage_tile(lds_t* lds, const T* __restrict__ src, int n, int H, int W, int C, int c0,
-                                           int ng, int h0, int w0) {
-  const u16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll 4
-  for (int i = threadIdx.x; i < RH * RW * NG; i += 256) {
-    const int p = i >> 3, g = i & 7;
-    const int h = h0 + p / RW, x = w0 + p % RW;
-    u16x8 v = z;
-    if (g < ng && (unsigned)h < (unsigned)H && (unsigned)x < (unsigned)W)
-      v = *reinterpret_cast<const u16x8*>(src + (((size_t)n * H + h) * W + x) * C + c0 + 8 * g);
-    *reinterpret_cast<u16x8*>(lds + p * PS + 8 * g) = v;
-  }
 }
 
 struct Dims {
@@ -406,13 +354,6 @@ static dim3 tile_grid(Dims& d, int oh, int ow, int th, int tw) {
   d.per = (int)std::min<long long>(16, std::max<long long>(1, total * blocks / 1024));
   return dim3((unsigned)((total + d.per - 1) / d.per), (unsigned)blocks);
 }
-
-// bf16 / fp16 only: check_act has refused everything else
-#define DWCONV_DISPATCH(t, ...)                                                \
-  do {                                                                         \
-    if ((t).scalar_type() == at::kBFloat16) { typedef __hip_bfloat16 T; __VA_ARGS__; } \
-    else { typedef __half T; __VA_ARGS__; }                                    \
-  } while (0)
 
 template <typename T>
 static void launch_fwd(const at::Tensor& x, const at::Tensor& w, at::Tensor& y, int stride, bool dgrad, dim3 grid,

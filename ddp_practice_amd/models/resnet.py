@@ -93,7 +93,7 @@ def _conv(x: torch.Tensor, conv: nn.Conv2d, cdtype: torch.dtype, bn: nn.Module |
         # grouped 3x3 (ResNeXt) on the block-diagonal MFMA kernels; the BN takes its own statistics
         return _gconv.conv_group(x, conv.weight, conv.stride[0], conv.groups, cdtype), None
     if _dwconv.usable(x, conv, cdtype):
-        # depthwise 3x3 (MobileNet) on the VALU granule kernels; the BN takes its own statistics
+        # depthwise 3x3 (MobileNet) / 5x5 (MnasNet) on the VALU granule kernels; the BN takes its own statistics
         return _dwconv.conv_dw(x, conv.weight, conv.stride[0], cdtype), None
     w = conv.weight.to(cdtype)
     out = F.conv2d(x, w, None if conv.bias is None else conv.bias.to(cdtype), conv.stride, conv.padding,
